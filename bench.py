@@ -21,7 +21,11 @@ does is recorded beside it (`tol_iteration_alone`: umass.png 1.6e-5, outside the
 is timed beside it (`kernels.precise`), and `relax_default` is the whole relaxation as the unchanged ROS plugin gets it
 (no environment: precise + red-black, bit-identical to harmonic_complete_cpu).
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run (`--gpus N --steps K --warmup W`) does what the headline needs and nothing else: set-up,
+the untimed develop sweeps, W warm-up steps, K timed steps, the line (metric, value, unit, ms_per_step = wall milliseconds per timed step,
+config, step_us_per_iteration, library).  `--dump-outputs DIR` also writes what the last timed step left (the field u, a fixed seeded
+sample of it when it is larger than 32 MB, and the delta of its check) as .npy files: the inputs are seeded, so two builds can be
+compared cell for cell.  Everything below is evidence beside the headline and runs only with `--full` (minutes):
   roofline      dominant kernel (sweep2d) vs the HBM roofline: 8 algorithmic bytes per grid cell per sweep
                 (read u once, write u once) / mean launch-to-launch device time, measured with HIP
                 events on the stream the kernels run on (epic_hip_timed_sweeps_gpu).  `traffic` = HBM bytes per launch
@@ -102,7 +106,37 @@ def parse():
     ap.add_argument("--no-maps", action="store_true", help="skip the timing of the reference's maps (BASELINE configs[0] / [1])")
     ap.add_argument("--no-node-flow", action="store_true", help="skip the navigation node's call sequence (1 check + 49 / 99 single updates per tick) on maze, umass and the timed grid")
     ap.add_argument("--only-config5", action="store_true", help="(internal) run only the 512^3 leg and print its object: the child of the PMC passes")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every evidence leg beside the headline (roofline with its kernel batches and PMC child passes, cpu_baseline, "
+                         "relax*, parity, config4 / config5, maps, node_flow; N > 1: the other scaling mode, the in-library child, the exchange "
+                         "probe): minutes.  Without it a run sets up, warms up, times the steps and prints the line; the --no-* options "
+                         "above pick among the legs of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them left -- the field u (float32; a fixed, seeded sample of %d of its "
+                         "cells in row-major order when the field is larger than that) and the delta of its check (float64) -- as "
+                         "DIR/u.npy and DIR/delta.npy (N > 1: DIR/u_rank<r>.npy of every rank's owned rows, DIR/delta.npy by rank 0)" % DUMP_CELLS)
+    args = ap.parse_args()
+    if not args.full:   # a plain run: the headline and nothing beside it
+        for leg in ("no_extra_legs", "no_cpu", "no_relax", "no_live_traffic", "no_parity", "no_config4", "no_maps", "no_node_flow"):
+            setattr(args, leg, True)
+    return args
+
+
+DUMP_CELLS = 1 << 23   # 32 MB of float32: inside the 64 MB an output dump may take
+DUMP_SEED = 20240601
+
+
+def dump_field(path, field, limit=DUMP_CELLS):
+    """--dump-outputs: `field` (a host array) as float32 to `path`; of a field of more than `limit` cells the cells at `limit`
+    flat indices drawn once from a generator seeded with DUMP_SEED (the same indices for the same shape in every run and build), ascending."""
+    import numpy as np
+
+    flat = np.ascontiguousarray(field, dtype=np.float32).ravel()
+    if flat.size > limit:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.size, limit))
+        flat = flat[idx]
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.save(path, flat)
 
 
 def cpu_baseline(m, u0, locked, half_sweeps, free_by_colour):
@@ -360,7 +394,7 @@ def live_traffic(args):
     child = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "1", "--warmup", "1", "--develop", "5000",
              "--size", str(args.size), "--stagger", str(args.stagger), "--math", args.math, "--scheme", args.scheme,
              "--rows-per-task", str(args.rows_per_task), "--no-cpu", "--no-relax", "--no-extra-legs", "--no-parity",
-             "--no-maps", "--no-node-flow", "--no-live-traffic"] + (["--track"] if args.track else [])
+             "--no-maps", "--no-node-flow", "--no-live-traffic", "--full"] + (["--track"] if args.track else [])
     env = dict(os.environ, TMPDIR="/tmp")
     try:
         # The library measures that height by timing, which a counter pass distorts.  So one plain child first, to learn the
@@ -604,7 +638,7 @@ def main():
         try:
             r2 = subprocess.run([sys.executable, os.path.abspath(__file__), "--in-library-child", str(world), "--steps", str(args.steps),
                                  "--math", args.math, "--size", str(args.size), "--develop", str(min(args.develop, 6000)),
-                                 "--stagger", str(args.stagger), "--no-live-traffic"],
+                                 "--stagger", str(args.stagger), "--no-live-traffic", "--full"],
                                 env=env, capture_output=True, text=True, timeout=600 if world >= 4 else 300)   # (well inside the other ranks' wait below)
             lines = [l for l in r2.stdout.splitlines() if l.startswith("{")]
             in_library = json.loads(lines[-1]) if lines else {"error": "rc %d: %s" % (r2.returncode, r2.stderr[-400:])}
@@ -1103,19 +1137,24 @@ def main():
         h, upload_s = abi_setup(grid, u0, locked, args.math, args.scheme, args.track)
         wall, dev_ms = abi_timed(h, args.steps, args.warmup)
         step_us_per_sweep = dev_ms * 1e3 / sweeps
-        # the dominant kernel on its own: a batch of plain iterations (no check) is launches of that kernel only -- the
-        # fused pass where the library fuses (two iterations per launch), the single sweep otherwise
+        if args.dump_outputs:   # the field and the delta the last timed step left, before anything else advances them
+            assert E.harmonic_get_potential_values_gpu(h) == 0
+            dump_field(os.path.join(args.dump_outputs, "u.npy"), h.u_array())
+            np.save(os.path.join(args.dump_outputs, "delta.npy"), np.array([float(h.delta)], dtype=np.float64))
         per_pass = max(1, int(E.epic_hip_iterations_per_pass(h)))
         library_dump = eh.config_dump(h)   # what the timed context was configured with and which path it is on, in the library's own words
-        batch = 2 * (args.stagger // 2)
-        kms, ms1 = 0.0, ct.c_float(0.0)
-        for _ in range(max(2, args.steps)):
-            assert E.epic_hip_timed_sweeps_gpu(h, batch, 0, ct.byref(ms1)) == 0
-            kms += ms1.value
-        launch_us = kms * 1e3 / (max(2, args.steps) * batch // per_pass)
         cells_per_launch = n * n if args.scheme == "jacobi" else n * n // 2   # cells one ITERATION recomputes
         single_us = None
-        if per_pass == 2:   # the single sweep of the same arithmetic, same run: what the fusion buys
+        if args.full:
+            # the dominant kernel on its own: a batch of plain iterations (no check) is launches of that kernel only -- the
+            # fused pass where the library fuses (two iterations per launch), the single sweep otherwise
+            batch = 2 * (args.stagger // 2)
+            kms, ms1 = 0.0, ct.c_float(0.0)
+            for _ in range(max(2, args.steps)):
+                assert E.epic_hip_timed_sweeps_gpu(h, batch, 0, ct.byref(ms1)) == 0
+                kms += ms1.value
+            launch_us = kms * 1e3 / (max(2, args.steps) * batch // per_pass)
+        if args.full and per_pass == 2:   # the single sweep of the same arithmetic, same run: what the fusion buys
             # (the library reads its environment once per context: a knob changed on a live one is announced -- include/epic_hip.h)
             os.environ["EPIC_HIP_NO_FUSE"] = "1"
             assert E.epic_hip_config_reload(h) == 0
@@ -1135,10 +1174,11 @@ def main():
                 "parallelism": "1 GPU", "h2d_seconds": round(upload_s, 3),
                 "fused_rows_per_task": int(E.epic_hip_fused_rows_per_task(h)),   # measured by the library on this grid
             },
-            "roofline": roofline(cells_per_launch, launch_us, args.math, args.scheme, True, per_pass),
             "step_us_per_iteration": round(step_us_per_sweep, 3),
             "library": library_dump,   # epic_hip_config_dump of the timed context: every EPIC_HIP_* knob as read, state, kernel path
         })
+        if args.full:
+            out["roofline"] = roofline(cells_per_launch, launch_us, args.math, args.scheme, True, per_pass)
         if library_dump:
             out["config"]["kernel_path"] = library_dump["path"]["plain_batch"]
         if single_us is not None:
@@ -1227,7 +1267,8 @@ def main():
             out["cpu_baseline"] = timed_leg("cpu_baseline", cpu_baseline, grid, u0, locked, args.cpu_half_sweeps, free_by_colour)
         LEG_SECONDS["whole run"] = round(time.perf_counter() - T_START, 1)
         out["leg_seconds"] = dict(LEG_SECONDS)
-        summarise_into_config(out)
+        if args.full:
+            summarise_into_config(out)
         print(json.dumps(out), flush=True)
         return
 
@@ -1236,7 +1277,7 @@ def main():
     # ---------------------------------------------------------------------------------------------------------
     from epic_amd.slab import SlabSolver
 
-    def slab_run(grid, steps, warmup, develop=develop, ramp=0.0):
+    def slab_run(grid, steps, warmup, develop=develop, ramp=0.0, dump=None):
         rows_each = grid[0] // world
         halo = args.halo or (8 if rows_each >= 4096 else 16 if rows_each >= 2048 else 32)
         solver = SlabSolver(grid, rank, world, device=torch.device("cuda", local), stagger=args.stagger,
@@ -1245,7 +1286,8 @@ def main():
         for _ in range(develop):
             solver.sweep(False)
         pair_rows = solver.tune_pairs() if develop >= min(grid) // 2 else 0   # on a developed field, as the library does
-        probe = solver.probe_exchange()   # BEFORE any timing: did the second stream's exchange overlap the interior sweep?
+        # (--full) BEFORE any timing: did the second stream's exchange overlap the interior sweep?
+        probe = solver.probe_exchange() if args.full else None
         while solver.iteration % args.stagger:   # (back to a step boundary: a step = one check + stagger - 1 plain iterations)
             solver.sweep(False)
         for _ in range(warmup):
@@ -1258,6 +1300,10 @@ def main():
         barrier()
         wall = time.perf_counter() - t0
         wall, dev_ms = max_over_ranks(wall, dev_ms)
+        if dump:   # every rank's owned rows of the field and the delta the last timed step left
+            dump_field(os.path.join(dump, "u_rank%d.npy" % rank), solver.owned(), DUMP_CELLS // world)
+            if rank == 0:
+                np.save(os.path.join(dump, "delta.npy"), np.array([float(solver.delta)], dtype=np.float64))
         if world > 1:
             f = torch.tensor([free], dtype=torch.int64, device=red_dev)
             dist.all_reduce(f)
@@ -1272,7 +1318,7 @@ def main():
     weak_first = args.weak and world > 1
     main_grid = [n * world, n] if weak_first else [n, n]
     _t_leg = time.perf_counter()
-    r = slab_run(main_grid, args.steps, args.warmup)
+    r = slab_run(main_grid, args.steps, args.warmup, dump=args.dump_outputs)
     LEG_SECONDS["headline: develop, tune, probe, timed steps"] = round(time.perf_counter() - _t_leg, 1)
     launch_us = r["dev_ms"] * 1e3 / sweeps
     actual_backend = dist.get_backend() if world > 1 else "none"

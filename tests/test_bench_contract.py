@@ -252,3 +252,42 @@ def test_plain_multi_gpu_command_starts_its_own_ranks_as_a_child():
     assert "no GPU visible" in r.stderr                      # said by a rank, i.e. the ranks were started
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert src.index("sys.exit(self_launch(args))") < src.index("import torch  # first")   # before torch is imported
+
+
+def test_a_plain_run_has_no_evidence_leg_and_full_has_them_all(monkeypatch):
+    """Without --full every leg beside the headline is switched off whatever else the command says; with it the --no-* options choose."""
+    import sys
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    legs = ("no_extra_legs", "no_cpu", "no_relax", "no_live_traffic", "no_parity", "no_config4", "no_maps", "no_node_flow")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2) and all(getattr(a, leg) for leg in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not any(getattr(a, leg) for leg in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-maps", "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.no_maps and not a.no_parity and a.dump_outputs == "somewhere"
+
+
+def test_an_output_dump_is_float32_whole_when_small_and_the_same_seeded_sample_when_large(tmp_path):
+    import sys
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    field = np.arange(12000, dtype=np.float64).reshape(100, 120) * 0.5
+    bench.dump_field(str(tmp_path / "d" / "whole.npy"), field)
+    whole = np.load(tmp_path / "d" / "whole.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, field.ravel().astype(np.float32))
+    for name in ("s1.npy", "s2.npy"):
+        bench.dump_field(str(tmp_path / "d" / name), field, limit=1000)
+    s1, s2 = np.load(tmp_path / "d" / "s1.npy"), np.load(tmp_path / "d" / "s2.npy")
+    assert s1.dtype == np.float32 and s1.shape == (1000,) and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) >= 0) and np.isin(s1, whole).all() and len(np.unique(s1)) > 900      # cells of the field, in row-major order
+    assert bench.DUMP_CELLS * 4 <= 64 * (1 << 20) // 2

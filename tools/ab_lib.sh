@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 ROUNDS=${ROUNDS:-2}
 for round in $(seq $ROUNDS); do
 for lib in "$@"; do
-  EPIC_LIB=$ROOT/$lib python3 $ROOT/bench.py --no-cpu --no-relax --no-parity --no-live-traffic --no-config4 --no-maps --steps 10 --warmup 2 2>/dev/null | python3 -c '
+  EPIC_LIB=$ROOT/$lib python3 $ROOT/bench.py --full --no-cpu --no-relax --no-parity --no-live-traffic --no-config4 --no-maps --steps 10 --warmup 2 2>/dev/null | python3 -c '
 import sys,json
 r=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=r.get("kernels",{}); g=lambda d,*ks: (g(d.get(ks[0],{}),*ks[1:]) if len(ks)>1 else d.get(ks[0])) if isinstance(d,dict) else None

@@ -5,7 +5,7 @@ export EPIC_HIP_STUDY=1   # the knobs below are study knobs: read only when aske
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/lds_reads; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="$ROOT/bench.py --no-cpu --no-relax --no-extra-legs --no-parity --no-live-traffic --steps 1 --warmup 1 --develop 5000"
+B="$ROOT/bench.py --full --no-cpu --no-relax --no-extra-legs --no-parity --no-live-traffic --steps 1 --warmup 1 --develop 5000"
 export EPIC_HIP_FUSED_ROWS=40
 for v in shipped "$@"; do
   lib=$ROOT/epic_amd/lib/libepic.so; [ "$v" != shipped ] && lib=$ROOT/gpurun_alt/$v/libepic.so

@@ -17,7 +17,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="$ROOT/bench.py --no-cpu --no-relax --no-extra-legs --no-parity --no-live-traffic --no-node-flow"
+B="$ROOT/bench.py --full --no-cpu --no-relax --no-extra-legs --no-parity --no-live-traffic --no-node-flow"
 C="$ROOT/tools/bench_config.py --grid 512 512 512 --develop 1500"
 SQ="SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY GRBM_GUI_ACTIVE"
 run() { name=$1; shift; if [ -n "$ONLY" ] && ! [[ "$name" =~ $ONLY ]]; then return 0; fi; "$@" > "$OUT/$name.log" 2>&1; echo "[$name] rc=$?"; }   # ONLY: a regex over the pass names

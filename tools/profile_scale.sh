@@ -18,7 +18,7 @@ for N in $NS; do
     mkdir -p "$OUT"
     python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $((29600 + N)) \
         --no-python rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d "$OUT" -o "%pid%" -- \
-        python3 "$ROOT/bench.py" --gpus "$N" --steps 3 --warmup 1 --develop 1000 --no-cpu "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+        python3 "$ROOT/bench.py" --gpus "$N" --steps 3 --warmup 1 --develop 1000 --full --no-cpu "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
     echo "[N=$N] rc=$?"
     tail -c 1500 "$OUT/bench.json"
     find "$OUT" -name "*kernel_trace.csv" -size +16M -delete
