@@ -587,7 +587,7 @@ hipError_t multi_run_pairs(Ctx *c, unsigned npairs, unsigned first, bool check_l
     note_iterations(c, first, 2 * npairs);
     const bool tol = c->math == 4;
     const int rpt = rb_pairs_rows_per_task(c);
-    const int nstrips_f = (c->pitch + 247) / 248;
+    const int nstrips_f = epic_hip::fused_2d_strips(c->pitch);
     if (c->last_lists != 2)
         for (auto &sl : c->slabs) sl.trk_f.force = std::max(sl.trk_f.force, 1);   // something else has touched the field since
     c->last_lists = 2;

@@ -48,7 +48,7 @@ int fused_rows_per_task(const Ctx *c)
 {
     if (c->rows_per_task > 0) return std::max(c->rows_per_task, 4);
     if (c->tuned_rows[2] > 0) return c->tuned_rows[2];   // (several devices: measured on the first slab)
-    const long long nstrips = (c->pitch + 247) / 248;
+    const long long nstrips = epic_hip::fused_2d_strips(c->pitch);
     long long r = (long long)c->rows * nstrips / 8192 / 8 * 8;
     return (int)std::min<long long>(64, std::max<long long>(16, r));
 }

@@ -59,9 +59,35 @@ hipError_t launch_wake_tile_range(const Activity *next_as_out, size_t tiles, int
 hipError_t launch_rb_fused_2d(const float *in, float *out, const uint32_t *maskw, int rows, int pitch, int rows_per_task,
                               int math, int parity, hipStream_t stream, const uint32_t *maskf = nullptr, const Activity *act = nullptr,
                               unsigned *delta_bits = nullptr, int check_begin = -1, int check_end = -1);   // check_*: as launch_sweep_2d (slabs)
+// Strip geometry of the fused passes (rb_fused2d_kernel, tol_fused_pass, fuse_masks_2d_kernel), stated once.  A wave holds 64 quads
+// of four columns; two iterations reach two columns far, so between two strips one quad on either side is a halo (loaded and
+// recomputed by both strips, stored by one): the strip stride is 62 quads = 248 columns, lane L of strip S holding columns
+// 248 S + 4 L .. + 3, i.e. quad 62 S + L of the row.  Lane 0 is the halo towards strip S - 1 and lane 63 the halo towards strip
+// S + 1 -- but at the two ENDS of a row there is no neighbouring strip and no halo is needed: column 0 and column pitch - 1 are
+// always locked (pack_mask_2d_kernel forces the border and the padding locked, set_cells_2d_kernel keeps them so), and the cell
+// next to either has all its neighbours inside the wave.  So strip 0 owns its lane 0, and lane 63 owns its quad where that is the
+// last of the row: 252 + 248 (n - 2) + 252 columns from n strips where the pitch is exactly that (256, 8192, 16128 ...: one strip
+// fewer than with a halo lane at the ends), 252 + 248 (n - 1) columns otherwise.
+constexpr int kFusedLaneCols = 4;                                  // columns per lane (one dwordx4)
+constexpr int kFusedStrideQuads = 62;                              // lanes between two strips' first lanes
+constexpr int kFusedStride = kFusedStrideQuads * kFusedLaneCols;   // 248 columns
+// the fewest strips that cover a row of `pitch` floats under the ownership rule (fused_2d_owns)
+__host__ __device__ inline int fused_2d_strips(int pitch)
+{
+    if (pitch <= 2 * kFusedLaneCols) return 1;
+    if ((pitch - 2 * kFusedLaneCols) % kFusedStride == 0) return (pitch - 2 * kFusedLaneCols) / kFusedStride;   // lane 63 of the last strip owns the last quad
+    return (pitch - kFusedLaneCols + kFusedStride - 1) / kFusedStride;
+}
+__host__ __device__ inline int fused_2d_quad0(int strip) { return strip * kFusedStrideQuads; }   // quad of the row in lane 0
+__host__ __device__ inline int fused_2d_col(int strip, int lane) { return (fused_2d_quad0(strip) + lane) * kFusedLaneCols; }   // first column of a lane
+// whether lane `lane` of strip `strip`, whose first column is `col`, stores (and counts) its four columns
+__host__ __device__ inline bool fused_2d_owns(int strip, int lane, int col, int pitch)
+{
+    return col < pitch && (lane >= 1 || strip == 0) && (lane <= kFusedStrideQuads || col + kFusedLaneCols == pitch);
+}
 inline size_t rb_fused_2d_tiles(int rows, int pitch, int rows_per_task)
 {
-    return (size_t)((pitch + 247) / 248) * (size_t)((rows + rows_per_task - 1) / rows_per_task);
+    return (size_t)fused_2d_strips(pitch) * (size_t)((rows + rows_per_task - 1) / rows_per_task);
 }
 // Two iterations in one pass (tol math only): in = u_k, out = u_{k+2}; in != out.  parity < 0: Jacobi; 0 / 1: the reference's
 // red-black scheme, parity = the first iteration's number & 1 (both colours are swept, the first one first).
@@ -71,10 +97,11 @@ inline size_t rb_fused_2d_tiles(int rows, int pitch, int rows_per_task)
 hipError_t launch_jacobi_fused_2d(const float *in, float *out, const uint32_t *maskw, int rows, int pitch, int rows_per_task,
                                   int math, hipStream_t stream, int parity = -1, const uint32_t *maskf = nullptr,
                                   const Activity *act = nullptr, unsigned *delta_bits = nullptr, int check_begin = -1, int check_end = -1);
-// Fused layout: a fused pass cuts a row into strips of 248 columns, lane L of strip S holding columns 248 S - 4 + 4 L .. + 3
-// (lanes 0 and 63 are halo lanes); per row and such strip four 64-bit words as in the standard layout (bit L of word j =
-// cell 4 L + j of that mapping).  Derived from the standard masks after every upload and every edit.
-inline size_t mask_words_fused_2d(int rows, int pitch) { return (size_t)rows * (size_t)((pitch + 247) / 248) * 8u; }
+// Fused layout: the masks cut for the fused passes' lane -> column mapping (strip geometry above: lane L of strip S holds columns
+// 248 S + 4 L .. + 3); per row and each of the fused_2d_strips(pitch) strips four 64-bit words as in the standard layout (bit L of
+// word j = cell 4 L + j of that mapping; bits of cells past the pitch are unspecified).  Derived from the standard masks after
+// every upload and every edit.
+inline size_t mask_words_fused_2d(int rows, int pitch) { return (size_t)rows * (size_t)fused_2d_strips(pitch) * 8u; }
 hipError_t launch_fuse_masks_2d(const uint32_t *maskw, int rows, int pitch, uint32_t *maskf, hipStream_t stream);
 hipError_t launch_eval_math(const float *in, float *out, size_t n, int which, hipStream_t stream);
 hipError_t launch_pack_mask_2d(const uint32_t *locked, int rows, int cols, int pitch, int ghost_top,
@@ -167,7 +194,7 @@ constexpr int kTolTripRows = (kTolRowsAhead + 3) % 2 == 0 ? kTolRowsAhead + 3 : 
 // 4096 x 8192: 42.8 / 42.3 / 40.0 / 38.3 / 37.9 / 37.8 / 38.0 / 39.0;  8192 x 8192 (per launch of two): 35: 172, 40: 163, 44: 164, 48: 166, 64: 167.
 inline int jacobi_fused_auto_rows(int rows, int pitch)
 {
-    const long long nstrips = (pitch + 247) / 248, slots = 4096;
+    const long long nstrips = fused_2d_strips(pitch), slots = 4096;
     const long long r = (long long)rows * nstrips / slots;
     return (int)(r < 12 ? 12 : r > 40 ? 40 : r);
 }

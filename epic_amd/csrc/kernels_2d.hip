@@ -446,16 +446,17 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, (SweepOcc<CHECK, MATH, RB, 
 // its strip it first recomputes the first colour ("A") of row r+1 from old values, then the second colour ("B") of row
 // r from the fresh A values of rows r-1, r, r+1 -- exactly the values the second half-sweep of the reference would
 // read -- and stores row r.  Waves stay independent because each one recomputes the A cells its B cells need itself:
-//   * columns: a wave loads 256 columns but owns only the 248 in lanes 1..62; lanes 0 and 63 are halo lanes whose
-//     innermost A cell feeds the neighbouring owned lane through the same DPP shift (strip stride 248, ~3 % lanes);
+//   * columns: a wave loads 256 columns and owns the 248 in lanes 1..62; towards a neighbouring strip lanes 0 and 63 are halo
+//     lanes whose innermost A cell feeds the neighbouring owned lane through the same DPP shift (strip stride 248, ~3 % lanes);
+//     at the two ends of a row there is no neighbour and the outer lane is owned too (kernels.h: strip geometry);
 //   * rows: a task recomputes A of the row above and below its chunk (4 extra row loads, 2 extra A rows per chunk).
 // Ping-pong (in != out) is required: a neighbouring task must still find the OLD values of the rows/columns it
 // recomputes.  Arithmetic per cell is the half-sweep's, so results are bit-identical to two in-place half-sweeps
 // (and, with the precise math, to two iterations of the reference CPU solver).
-constexpr int kFusedOut = 248;  // owned columns per wave
+static_assert(kFusedLaneCols == kColsPerLane && kFusedStrideQuads == kWave - 2, "kernels.h states the strip geometry for this wave");
 
 // TRACK (round 4): the pass with work lists, as the plain sweep has them (wake.h) -- a tile is one task of THIS kernel
-// (rows_per_task rows x 248 owned columns); it runs in a pass only if the previous pass changed a value it reads, and two
+// (rows_per_task rows x its strip's owned columns, 248 or at a row's end 252); it runs in a pass only if the previous pass changed a value it reads, and two
 // iterations reach two cells far: its own cells, the two nearest rows of the tiles above and below, the two nearest columns
 // of the tiles left and right, and the one corner cell of each diagonal neighbour.  A tile that is skipped holds, in BOTH
 // buffers, the values the pass would have written (it did not change in the previous pass, and nothing it reads did).  The
@@ -499,16 +500,17 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void rb_fused2d_kernel(Swee
     const int chunk = task / a.nstrips;
     const int r0 = a.row_begin + chunk * a.rows_per_task + min(chunk, a.chunk_rem);
     const int r1 = min(r0 + a.rows_per_task + (chunk < a.chunk_rem ? 1 : 0), a.row_end);
-    const int col = strip * kFusedOut - kColsPerLane + lane * kColsPerLane;  // lane 0 = left halo lane
-    const int lcol = min(max(col, 0), a.pitch - kColsPerLane);
-    const bool owner = lane >= 1 && lane <= kWave - 2 && col < a.pitch;
+    // kernels.h, strip geometry: lanes 0 and 63 are halo lanes towards a neighbouring strip and owned at the two ends of a row
+    const int col = fused_2d_col(strip, lane);
+    const int lcol = min(col, a.pitch - kColsPerLane);
+    const bool owner = fused_2d_owns(strip, lane, col, a.pitch);
     const lmask owners = (TRACK || CHECK) ? __builtin_amdgcn_ballot_w64(owner) : 0;
 
     // rows through buffer descriptors with scalar row offsets, as in the plain sweep (no VALU address arithmetic)
     const int rlo = max(r0 - 2, 0);  // rows r0 - 2 .. r1 + 2 are touched
     const __amdgpu_buffer_rsrc_t rin = raw_buffer(a.in + (size_t)rlo * pitch), rout = raw_buffer(a.out + (size_t)rlo * pitch);
     const unsigned lane_off = (unsigned)lcol * 4u;
-    // Stores: the halo lanes (and lanes past the last column) must not write.  A branch around the store would do -- and did,
+    // Stores: the lanes that own nothing (halo lanes, lanes past the last column) must not write.  A branch around the store would do -- and did,
     // until the ISA showed what it costs: with a store that may or may not have been issued the compiler can no longer count
     // the memory operations in flight behind the row it is waiting for, waits for vmcnt(0) / vmcnt(1) at the top of every step,
     // and with that for the acknowledgement of the store issued a moment ago (share of wave cycles at s_waitcnt 0.37 -> 0.28 with
@@ -522,16 +524,18 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void rb_fused2d_kernel(Swee
         const vu4 q = __builtin_amdgcn_raw_buffer_load_b128(rin, lane_off, row_off(r), 0);
         return make_float4(u2f(q.x), u2f(q.y), u2f(q.z), u2f(q.w));
     };
-    // Lane masks of row r for THIS kernel's lane -> column mapping (lane L holds quad strip * 62 - 1 + L of the row,
+    // Lane masks of row r for THIS kernel's lane -> column mapping (lane L holds quad strip * 62 + L of the row,
     // the stored masks are cut at multiples of 64 quads): a funnel shift of two neighbouring words, all scalar.
-    // Lanes outside the row (lane 0 of strip 0, lanes past the last column) get arbitrary bits: nothing they compute
-    // is stored or reaches an unlocked cell.
+    // Lanes outside the row (past the last column) get arbitrary bits: nothing they compute is stored or reaches an
+    // unlocked cell.  The outer cell of an edge lane has no neighbour in the wave on one side and the shift gives it zero
+    // there; where that lane is owned (the two ends of a row) the cell is column 0 or column pitch - 1, always locked:
+    // what is computed for it is discarded by the lock select.
     // In two phases, as in tol_fused_pass below: the words are FETCHED a step before they are CUT (no scalar-memory round trip
     // in the middle of a step); FMASK: the library's second copy of the masks, already cut for this mapping (kernels.h).
     struct RowMask { lmask m0, m1, m2, m3; };
     struct RowMaskRaw { lmask lo0, lo1, lo2, lo3, hi0, hi1, hi2, hi3; };
-    const int g0 = strip * (kFusedOut / kColsPerLane) - 1;
-    const int sw = max(g0, 0) >> 6, sh = max(g0, 0) & 63, sw1 = min(sw + 1, nstd - 1);
+    const int g0 = fused_2d_quad0(strip);   // the strip's first quad: inside the row (fused_2d_strips leaves no strip without a column)
+    const int sw = g0 >> 6, sh = g0 & 63, sw1 = min(sw + 1, nstd - 1);
     auto mask_fetch = [&](int r) -> RowMaskRaw {
         r = min(max(r, 0), rlast);
         if (FMASK) {
@@ -544,8 +548,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void rb_fused2d_kernel(Swee
     auto mask_cut = [&](const RowMaskRaw &w) -> RowMask {
         if (FMASK) return RowMask{w.lo0, w.lo1, w.lo2, w.lo3};
         auto cut = [&](lmask lo, lmask hi) -> lmask {   // (lo >> sh) | (hi << (64 - sh)), branch-free for sh = 0
-            const lmask m = (lo >> sh) | ((hi << 1) << (63 - sh));
-            return g0 < 0 ? m << 1 : m;
+            return (lo >> sh) | ((hi << 1) << (63 - sh));
         };
         return RowMask{cut(w.lo0, w.hi0), cut(w.lo1, w.hi1), cut(w.lo2, w.hi2), cut(w.lo3, w.hi3)};
     };
@@ -553,7 +556,9 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void rb_fused2d_kernel(Swee
     // what this task changed, as the tiles around it need to know it (TRACK): lane masks and flags in scalar registers
     lmask chg_any = 0, chg_top = 0, chg_bot = 0;
     bool chg_left = false, chg_right = false, c_tl = false, c_tr = false, c_bl = false, c_br = false;
-    constexpr lmask kFirstOwned = 2ull, kLastOwned = 1ull << (kWave - 2);   // lanes 1 and 62
+    // lanes 1 and 62: the owned lanes next to a NEIGHBOURING strip.  (An edge strip also owns lane 0 or 63, but has no neighbour
+    // on that side -- lf_ok / rt_ok below --; what those lanes change reaches chg_any / chg_top / chg_bot through `owners`.)
+    constexpr lmask kFirstOwned = 2ull, kLastOwned = 1ull << (kWave - 2);
     // One colour of one row.  second = false: colour A (iteration it), true: colour B (iteration it + 1).
     // owned: the row belongs to this task (level A is also computed for the row above and the row below the chunk).
     auto stage = [&](int r, bool second, bool owned, const float4 &up, const float4 &c, const float4 &dn, const RowMask &k) -> float4 {
@@ -656,7 +661,8 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void rb_fused2d_kernel(Swee
 // rows r .. r+2 of u_k (level A, kept in registers only), then iteration k+2 of row r from rows r-1 .. r+1 of level A
 // (level B), and stores row r.  4 B per cell-update; the price is arithmetic done twice where tasks meet:
 //   * columns: a wave loads 256 columns and owns the 248 in lanes 1..62 (as rb_fused2d_kernel); the inner cell of each
-//     halo lane is a correct level-A value (its own neighbours are all inside the 256), everything further out is unused;
+//     halo lane is a correct level-A value (its own neighbours are all inside the 256), everything further out is unused.
+//     At the two ends of a row the outer lane is owned as well (kernels.h, strip geometry: 8192 columns are 33 strips, not 34);
 //   * rows: a task computes level A for the row above and the row below its chunk as well (rows r0-1 .. r1 of level A
 //     from rows r0-2 .. r1+1 of u_k).
 // Every cell value is produced by the same tol_update_2d on the same inputs as in two single sweeps, so the result is
@@ -704,13 +710,14 @@ __device__ __forceinline__ void tol_fused_pass(const Sweep2dArgs &a, TolLnEntry 
     const int chunk = task / a.nstrips;
     const int r0 = a.row_begin + chunk * a.rows_per_task + min(chunk, a.chunk_rem);
     const int r1 = min(r0 + a.rows_per_task + (chunk < a.chunk_rem ? 1 : 0), a.row_end);
-    const int col = strip * kFusedOut - kColsPerLane + lane * kColsPerLane;  // lane 0 = left halo lane
-    const int lcol = min(max(col, 0), a.pitch - kColsPerLane);
-    const bool owner = lane >= 1 && lane <= kWave - 2 && col < a.pitch;
+    // kernels.h, strip geometry: lanes 0 and 63 are halo lanes towards a neighbouring strip and owned at the two ends of a row
+    const int col = fused_2d_col(strip, lane);
+    const int lcol = min(col, a.pitch - kColsPerLane);
+    const bool owner = fused_2d_owns(strip, lane, col, a.pitch);
     const lmask owners = (TRACK || CHECK) ? __builtin_amdgcn_ballot_w64(owner) : 0;
     lmask chg_any = 0, chg_top = 0, chg_bot = 0;   // what this task changed (TRACK): lane masks and flags in scalar registers
     bool chg_left = false, chg_right = false, c_tl = false, c_tr = false, c_bl = false, c_br = false;
-    constexpr lmask kFirstOwned = 2ull, kLastOwned = 1ull << (kWave - 2);   // lanes 1 and 62
+    constexpr lmask kFirstOwned = 2ull, kLastOwned = 1ull << (kWave - 2);   // lanes 1 and 62, next to a neighbouring strip (as rb_fused2d_kernel)
     const int rlast = a.rows - 1;
     const size_t pitch = (size_t)a.pitch;
     typedef unsigned vu4 __attribute__((ext_vector_type(4)));
@@ -718,7 +725,7 @@ __device__ __forceinline__ void tol_fused_pass(const Sweep2dArgs &a, TolLnEntry 
     const int rlo = max(r0 - 2, 0);  // rows r0 - 2 .. r1 + 4 are touched (clamped to the grid)
     const __amdgpu_buffer_rsrc_t rin = raw_buffer(a.in + (size_t)rlo * pitch), rout = raw_buffer(a.out + (size_t)rlo * pitch);
     const unsigned lane_off = (unsigned)lcol * 4u;
-    // Stores: the halo lanes (and lanes past the last column) must not write.  A branch around the store would do -- and did,
+    // Stores: the lanes that own nothing (halo lanes, lanes past the last column) must not write.  A branch around the store would do -- and did,
     // until the ISA showed what it costs: with a store that may or may not have been issued the compiler can no longer count
     // the memory operations in flight behind the row it is waiting for, waits for vmcnt(0) / vmcnt(1) at the top of every step,
     // and with that for the acknowledgement of the store issued a moment ago (share of wave cycles at s_waitcnt 0.37 -> 0.28 with
@@ -732,7 +739,7 @@ __device__ __forceinline__ void tol_fused_pass(const Sweep2dArgs &a, TolLnEntry 
         const vu4 q = __builtin_amdgcn_raw_buffer_load_b128(rin, lane_off, row_off(r), 0);
         return make_float4(u2f(q.x), u2f(q.y), u2f(q.z), u2f(q.w));
     };
-    // lane masks of a row for this kernel's lane -> column mapping (lane L holds quad strip * 62 - 1 + L of the row, the stored
+    // lane masks of a row for this kernel's lane -> column mapping (lane L holds quad strip * 62 + L of the row, the stored
     // masks are cut at multiples of 64 quads): a funnel shift of two neighbouring mask words, all scalar.  In two phases: the
     // eight words are FETCHED (two s_load_dwordx8, nothing depends on them yet) at the top of a step and CUT at its end.
     // (As one function with a test of `sh` between the loads -- round 2 -- the wave made eight scalar-memory round trips in a
@@ -741,8 +748,8 @@ __device__ __forceinline__ void tol_fused_pass(const Sweep2dArgs &a, TolLnEntry 
     struct RowMask { lmask m0, m1, m2, m3; };
     struct RowMaskRaw { lmask lo0, lo1, lo2, lo3, hi0, hi1, hi2, hi3; };
     const int nstd = a.pitch >> 8;
-    const int g0 = strip * (kFusedOut / kColsPerLane) - 1;
-    const int sw = max(g0, 0) >> 6, sh = max(g0, 0) & 63, sw1 = min(sw + 1, nstd - 1);
+    const int g0 = fused_2d_quad0(strip);   // the strip's first quad: inside the row (fused_2d_strips leaves no strip without a column)
+    const int sw = g0 >> 6, sh = g0 & 63, sw1 = min(sw + 1, nstd - 1);
     // (FMASK: the library keeps a second copy of the masks already cut for this mapping -- kernels.h, fused layout --, one
     // s_load_dwordx8 per row and no shifts; the funnel remains for callers that hold the standard layout only)
     auto mask_fetch = [&](int r) -> RowMaskRaw {
@@ -757,16 +764,14 @@ __device__ __forceinline__ void tol_fused_pass(const Sweep2dArgs &a, TolLnEntry 
     auto mask_cut = [&](const RowMaskRaw &w) -> RowMask {
         if (FMASK) return RowMask{w.lo0, w.lo1, w.lo2, w.lo3};
         // (lo >> sh) | (hi << (64 - sh)) without a branch for sh = 0: (hi << 1) << (63 - sh) is 0 there
-        auto cut = [&](lmask lo, lmask hi) -> lmask {
-            const lmask m = (lo >> sh) | ((hi << 1) << (63 - sh));
-            return g0 < 0 ? m << 1 : m;
-        };
+        auto cut = [&](lmask lo, lmask hi) -> lmask { return (lo >> sh) | ((hi << 1) << (63 - sh)); };
         return RowMask{cut(w.lo0, w.hi0), cut(w.lo1, w.hi1), cut(w.lo2, w.hi2), cut(w.lo3, w.hi3)};
     };
     auto row_mask = [&](int r) -> RowMask { return mask_cut(mask_fetch(r)); };
-    // One iteration of one row from its three rows and their splits.  The outer cells of the halo lanes have no neighbour
-    // on one side: the shift gives them zero bits there (bound_ctrl: one instruction, no edge operand to set up) -- their
-    // results are never stored and never read by an owned cell.
+    // One iteration of one row from its three rows and their splits.  The outer cells of lanes 0 and 63 have no neighbour
+    // on one side: the shift gives them zero bits there (bound_ctrl: one instruction, no edge operand to set up).  In a halo
+    // lane their results are never stored and never read by an owned cell; where the lane is owned (the two ends of a row)
+    // the cell is column 0 or column pitch - 1, which is always locked: the lock select discards what was computed for it.
     auto shl = [](float v) { return u2f(__builtin_amdgcn_mov_dpp(f2u(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, true)); };  // from the left
     auto shr = [](float v) { return u2f(__builtin_amdgcn_mov_dpp(f2u(v), 0x130 /* wave_shl:1 */, 0xf, 0xf, true)); };  // from the right
     // (red-black: `odd_cols` says which half of the row this level recomputes -- .y / .w or .x / .z; scalar)
@@ -936,18 +941,16 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, 3) void tol_fused2d_tracked
 // masks: one thread per (row, fused strip, word), the funnel shift the passes would otherwise do per row and wave.
 __global__ void fuse_masks_2d_kernel(const uint32_t *maskw, int rows, int pitch, uint32_t *maskf)
 {
-    const int nstd = pitch >> 8, nfused = (pitch + kFusedOut - 1) / kFusedOut;
+    const int nstd = pitch >> 8, nfused = fused_2d_strips(pitch);
     const size_t n = (size_t)rows * nfused * 4, i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int j = (int)(i & 3), strip = (int)((i >> 2) % nfused);
     const size_t r = (i >> 2) / nfused;
-    const int g0 = strip * (kFusedOut / kColsPerLane) - 1;
-    const int sw = max(g0, 0) >> 6, sh = max(g0, 0) & 63, sw1 = min(sw + 1, nstd - 1);
+    const int g0 = fused_2d_quad0(strip);   // the strip's first quad: inside the row (fused_2d_strips leaves no strip without a column)
+    const int sw = g0 >> 6, sh = g0 & 63, sw1 = min(sw + 1, nstd - 1);
     const unsigned long long *std64 = reinterpret_cast<const unsigned long long *>(maskw);
     const unsigned long long lo = std64[(r * nstd + sw) * 4 + j], hi = std64[(r * nstd + sw1) * 4 + j];
-    unsigned long long m = (lo >> sh) | ((hi << 1) << (63 - sh));
-    if (g0 < 0) m <<= 1;
-    reinterpret_cast<unsigned long long *>(maskf)[i] = m;
+    reinterpret_cast<unsigned long long *>(maskf)[i] = (lo >> sh) | ((hi << 1) << (63 - sh));
 }
 
 // uint32-per-cell mask (the ABI's format, rows x cols, unpitched) -> lane masks (kernels.h).  One wave per (row,
@@ -1073,8 +1076,8 @@ int resident_blocks_of(const void *kernel)
 
 // The fused passes without work lists: how many chunks the rows are cut into.  A launch's workgroups (four waves, one per SIMD) are dealt
 // over the CUs, so what a launch costs is the CU with the most blocks: ceil(blocks / CUs) of them, each as long as its chunk is high.
-// 8192 rows at 40 per task are 205 chunks x 34 strips = 1743 blocks = 6.81 per CU -- seven on most CUs; 210 chunks still make seven
-// (1785 blocks = 6.97) and are 39 rows high.  So: the most chunks that keep ceil(blocks / CUs) where the requested height puts it, the
+// 8192 rows at 40 per task are 205 chunks x 33 strips = 1692 blocks = 6.61 per CU -- seven on most CUs; 217 chunks still make seven
+// (1791 blocks = 6.996) and are 37-38 rows high (with the 34 strips of the geometry before the edge lanes were owned: 210 x 39).  So: the most chunks that keep ceil(blocks / CUs) where the requested height puts it, the
 // rows dealt evenly over them (heights q and q + 1, never above the requested one).  Measured (profiles/r05_experiments.txt item 15):
 // the pass steps up by 7-10 % where one block more than a multiple of the CU count appears (54 -> 55, 68 -> 69 rows per task), and
 // 8190 rows = 210 x 39 run 1.4 % faster than as 205 x 40.  EPIC_HIP_FLAGS bit 2 (default on) switches it.
@@ -1230,7 +1233,7 @@ hipError_t launch_rb_fused_2d(const float *in, float *out, const uint32_t *maskw
     a.rows_per_task = rows_per_task;
     a.chunk_rem = 0;   // (one workgroup per block here, dealt as they finish: with the tol passes' chunk tightening the measured heights lie
                        //  within 156-163 us instead of 147-160, and whole relaxations take the same 2.306 s -- not used; item 15)
-    a.nstrips = (pitch + kFusedOut - 1) / kFusedOut;
+    a.nstrips = fused_2d_strips(pitch);
     a.nchunks = (rows + rows_per_task - 1) / rows_per_task;
     a.flags = sweep_flags();
     a.ntasks = a.nstrips * a.nchunks;
@@ -1295,7 +1298,7 @@ hipError_t launch_jacobi_fused_2d(const float *in, float *out, const uint32_t *m
     a.row_end = rows;
     a.rows_per_task = rows_per_task;
     a.chunk_rem = 0;
-    a.nstrips = (pitch + kFusedOut - 1) / kFusedOut;
+    a.nstrips = fused_2d_strips(pitch);
     a.nchunks = (rows + rows_per_task - 1) / rows_per_task;
     a.flags = sweep_flags();
     if (!act) tighten_chunks(a, rows);   // (work lists number uniform tiles: those launches keep the requested height)

@@ -218,7 +218,8 @@ int epic_hip_sweep_2d(const float *d_in, float *d_out, const uint32_t *d_maskw, 
  * rows_per_task = 0: the library's choice for this size. */
 int epic_hip_sweep2_2d(const float *d_in, float *d_out, const uint32_t *d_maskw, unsigned int rows, unsigned int pitch,
                        unsigned int rows_per_task, int math_mode, void *stream);
-/* The masks a second time, cut for the fused passes' lane -> column mapping (strips of 248 columns): epic_hip_sweeps_2d takes
+/* The masks a second time, cut for the fused passes' lane -> column mapping (lane L of strip S holds columns 248 S + 4 L .. + 3; as
+ * many strips as cover the row when the first strip owns its lane 0 and the last one the row's last quad): epic_hip_sweeps_2d takes
  * them as d_maskf and then skips a funnel shift of two mask words per row and wave (NULL: it shifts, as epic_hip_sweep2_2d,
  * which has no such parameter, always does -- a different instantiation of the pass: time and tune through the call you run).
  * epic_hip_mask_words_fused_2d(rows, pitch) uint32 words; derive after every epic_hip_pack_mask_2d. */
