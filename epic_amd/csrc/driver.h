@@ -27,6 +27,8 @@
 //                        handover and the tol mode's finishing iterations; set_cells
 //   driver_ext.hip       the extension entry points of include/epic_hip.h (batches, timing, mode selection, reports, raw operators)
 // All of it is host code: tests/test_host_driver_faults.py compiles these files unchanged with g++ against a fake HIP runtime.
+//   occupancy_driver.hip the dense occupancy ingestion of include/epic_hip.h (a map message's bytes onto the resident state); not one of
+//                        the driver_* units above: it calls launchers the fake runtime does not know
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>

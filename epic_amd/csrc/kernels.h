@@ -113,6 +113,19 @@ hipError_t launch_set_cells_2d(float *u, uint32_t *maskw, int rows, int cols, in
                                const unsigned *v, const unsigned *types, hipStream_t stream, int row0 = 0, int grid_rows = 0,
                                int pin_top = 0, int pin_bottom = 0);
 
+// ---- dense occupancy ingestion (occupancy_2d.hip) ----------------------------------------------
+// A map message's bytes (d_occ: rows rows of occ_pitch bytes on the device, occ_pitch >= cols) applied to u and the lane masks
+// by the rule of occupancy_rule.h; d_changed (may be null, zero it first) receives the count the header defines, spread over
+// kOccCounters words kOccCounterStride apart (a 128-byte line each): the sum is the count.  One word took every wave's atomic
+// -- 240 000 of them at 8192^2 with 1 % of the cells flipped -- and cost 2.9 ms of a kernel that moves its data in 0.1.  The
+// fused masks are NOT rebuilt: launch_fuse_masks_2d afterwards.  Called from occupancy_driver.hip only.
+constexpr int kOccCounters = 256, kOccCounterStride = 16;
+constexpr size_t kOccCounterBytes = (size_t)kOccCounters * kOccCounterStride * sizeof(unsigned long long);
+hipError_t launch_occupancy_2d(float *u, uint32_t *maskw, const unsigned char *d_occ, size_t occ_pitch, int rows, int cols, int pitch,
+                               int obstacle_threshold, int no_change, unsigned flags, unsigned long long *d_changed, hipStream_t stream);
+// u = EPIC_LOG_SPACE_FREE wherever the mask bit is clear
+hipError_t launch_reset_free_cells_2d(float *u, const uint32_t *maskw, int rows, int cols, int pitch, hipStream_t stream);
+
 // ---- small grids: several iterations per launch on LDS tiles (kernels_tile2d.hip) ----------------
 // A tile owns tile_rows x tile_cols cells and carries `halo` ghost rings; a launch performs up to `halo` iterations.
 struct TilePlan { int halo, tile_rows, tile_cols, tiles_r, tiles_c; };   // halo == 0: no plan (grid or halo out of range)

@@ -134,6 +134,12 @@ _SIGNATURES = {
                                       ct.POINTER(ct.c_int), ct.POINTER(ct.c_float)),
     "epic_hip_compute_path_2d_gpu": (_H, ct.c_float, ct.c_float, ct.c_float, ct.c_float, ct.c_uint, _UP,
                                      ct.POINTER(ct.POINTER(ct.c_float))),
+    "epic_hip_set_occupancy_2d_cpu": (_H, ct.c_void_p, ct.c_int, ct.c_int, ct.c_uint, ct.POINTER(ct.c_ulonglong)),
+    "epic_hip_set_occupancy_2d_gpu": (_H, ct.c_void_p, ct.c_int, ct.c_int, ct.c_uint, ct.POINTER(ct.c_ulonglong)),
+    "epic_hip_timed_occupancy_2d_gpu": (_H, ct.c_void_p, ct.c_int, ct.c_int, ct.c_uint, ct.POINTER(ct.c_ulonglong),
+                                        ct.POINTER(ct.c_float)),
+    "epic_hip_reset_free_cells_2d_cpu": (_H,),
+    "epic_hip_reset_free_cells_2d_gpu": (_H,),
     "epic_hip_activity_stats": (_H, ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_ulonglong)),
     "epic_hip_activity_stats2": (_H, ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_ulonglong)),
     "epic_hip_work_done": (_H, ct.POINTER(ct.c_double), ct.c_int),
@@ -185,6 +191,10 @@ SCHEME_REDBLACK = 1
 EPIC_CELL_TYPE_GOAL = 0
 EPIC_CELL_TYPE_OBSTACLE = 1
 EPIC_CELL_TYPE_FREE = 2
+# flags of epic_hip_set_occupancy_2d_* (include/epic_hip.h)
+EPIC_HIP_OCC_KEEP_FREE = 1
+EPIC_HIP_OCC_UNSIGNED = 2
+EPIC_HIP_OCC_OVER_GOALS = 4
 
 
 def config_dump(h):

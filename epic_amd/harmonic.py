@@ -106,6 +106,42 @@ class Harmonic(eh.EpicHarmonic):
             raise ValueError("process must be 'gpu' or 'cpu'")
         return timing
 
+    # -- map messages ---------------------------------------------------------------------------------------
+    def set_occupancy(self, occ, obstacle_threshold=50, no_change=-2, keep_free=False, unsigned=False, over_goals=False,
+                      process='gpu'):
+        """Apply a map message (one byte per cell, shape m) by the rule of epic_hip_set_occupancy_2d_* (include/epic_hip.h):
+        the defaults are the navigation node's /map callback; ``unsigned=True, over_goals=True, obstacle_threshold=250,
+        no_change=-1`` is the nav_core plugin's costmap rule.  ``process``: 'cpu' edits the host arrays, 'gpu' the
+        device-resident state, 'both' the host arrays and then the device state, as the node does.  ``keep_free``: cells
+        that stay free keep their potential (warm start).  Returns ``changed`` (of the device call for 'both')."""
+        if process not in ('gpu', 'cpu', 'both'):
+            raise ValueError("process must be 'gpu', 'cpu' or 'both'")
+        occ = np.ascontiguousarray(np.asarray(occ, dtype=np.uint8 if unsigned else np.int8))
+        if occ.size != int(np.prod(self.shape)):
+            raise ValueError("occ must have prod(m) = %d elements" % int(np.prod(self.shape)))
+        flags = ((eh.EPIC_HIP_OCC_KEEP_FREE if keep_free else 0) | (eh.EPIC_HIP_OCC_UNSIGNED if unsigned else 0)
+                 | (eh.EPIC_HIP_OCC_OVER_GOALS if over_goals else 0))
+        changed = ct.c_ulonglong(0)
+        for variant, wanted in ((eh._epic.epic_hip_set_occupancy_2d_cpu, ('cpu', 'both')),
+                                (eh._epic.epic_hip_set_occupancy_2d_gpu, ('gpu', 'both'))):
+            if process in wanted:
+                rc = variant(self, occ.ctypes.data, int(obstacle_threshold), int(no_change), flags, ct.byref(changed))
+                if rc != 0:
+                    raise RuntimeError("epic_amd: %s failed with code %d" % (variant.__name__, rc))
+        return int(changed.value)
+
+    def reset_free_cells(self, process='gpu'):
+        """Every unlocked interior cell back to EPIC_LOG_SPACE_FREE (the node's reset_free_cells service); ``process`` as in
+        ``set_occupancy``."""
+        if process not in ('gpu', 'cpu', 'both'):
+            raise ValueError("process must be 'gpu', 'cpu' or 'both'")
+        for variant, wanted in ((eh._epic.epic_hip_reset_free_cells_2d_cpu, ('cpu', 'both')),
+                                (eh._epic.epic_hip_reset_free_cells_2d_gpu, ('gpu', 'both'))):
+            if process in wanted:
+                rc = variant(self)
+                if rc != 0:
+                    raise RuntimeError("epic_amd: %s failed with code %d" % (variant.__name__, rc))
+
     def __str__(self):
         s = "n: %d\nm: %s\nepsilon: %g\ndelta: %g\nnumIterationsToStaggerCheck: %d\ncurrentIteration: %d\n" % (
             self.n, list(self.shape), self.epsilon, self.delta, self.numIterationsToStaggerCheck,

@@ -134,6 +134,46 @@ int epic_hip_compute_paths_2d_gpu(EpicHarmonicT *harmonic, unsigned int n_paths,
 int epic_hip_compute_path_2d_gpu(EpicHarmonicT *harmonic, float x, float y, float stepSize, float cdPrecision,
                                  unsigned int maxLength, unsigned int *k, float **path);
 
+/* ---- dense occupancy-grid ingestion (2-D) -------------------------------------------------------------------------
+ * A map message applied where the state lives.  The reference's callers expand a message into a list of (x, y) pairs and a
+ * list of types with one entry per interior cell and hand both to harmonic_utilities_set_cells_2d_cpu / _gpu
+ * (src/epic_navigation_node_harmonic.cpp:383-426 subOccupancyGrid, :582-611 srvResetFreeCells; src/epic_nav_core_plugin.cpp:139-164
+ * setCellsFromCostmap): 12 bytes per cell over the bus for a message of 1.  These take the message's bytes.
+ *   occ   host pointer to m[0] x m[1] bytes, row-major and unpitched: msg->data / costmap->getCharMap().
+ * For every INTERIOR cell (1 <= y <= m[0] - 2, 1 <= x <= m[1] - 2), with v = the cell's byte widened to int (signed char;
+ * unsigned char with EPIC_HIP_OCC_UNSIGNED), in this order:
+ *   1. v == no_change: the cell is untouched (a no_change outside the byte's range switches the test off);
+ *   2. the cell is a goal (locked and u == 0.0f) and EPIC_HIP_OCC_OVER_GOALS is not set: untouched;
+ *   3. v >= obstacle_threshold: u = EPIC_LOG_SPACE_OBSTACLE, locked;
+ *   4. otherwise: unlocked, u = EPIC_LOG_SPACE_FREE -- except that with EPIC_HIP_OCC_KEEP_FREE a cell that was unlocked already
+ *      keeps the value it has: a converged field survives a message that changed three cells (warm start).
+ * Border cells are never touched.  flags 0, threshold 50, no_change -2 is subOccupancyGrid followed by setCells, cell for cell;
+ * UNSIGNED | OVER_GOALS, threshold 250 and a no_change out of range is setCellsFromCostmap.
+ *   *changed (may be NULL) receives the number of cells whose locked flag changed, or that stayed locked and changed their value
+ *   (goal <-> obstacle).
+ * The _cpu variants edit harmonic->u and harmonic->locked; the _gpu variants edit the device-resident state only (the current u
+ * buffer and the masks; the goal test reads the device state) -- the split of the reference's set_cells pair: a node calls both.
+ * The _gpu variants are ordering points like harmonic_utilities_set_cells_2d_gpu and synchronise.  With EPIC_HIP_OCC_KEEP_FREE
+ * and *changed == 0 the resident state is bit for bit what it was and a tracked relaxation goes on undisturbed; every other call
+ * makes the next two iterations run every tile.
+ * epic_hip_reset_free_cells_2d_*: every unlocked interior cell back to EPIC_LOG_SPACE_FREE (srvResetFreeCells).
+ * EPIC_ERROR_INVALID_DATA: a null harmonic, m, u, locked or occ, n != 2, (_gpu) no device state; HIP failures give the codes
+ * harmonic_utilities_set_cells_2d_gpu gives for the same steps. */
+#define EPIC_HIP_OCC_KEEP_FREE   1u  /* a cell that is unlocked before and free after keeps its potential (warm start) */
+#define EPIC_HIP_OCC_UNSIGNED    2u  /* bytes are unsigned char (costmap_2d costs); default: signed char (nav_msgs/OccupancyGrid) */
+#define EPIC_HIP_OCC_OVER_GOALS  4u  /* goal cells are overwritten like any other (the plugin's rule); default: goals are left alone (the node's rule) */
+int epic_hip_set_occupancy_2d_cpu(EpicHarmonicT *h, const void *occ, int obstacle_threshold, int no_change,
+                                  unsigned flags, unsigned long long *changed);
+int epic_hip_set_occupancy_2d_gpu(EpicHarmonicT *h, const void *occ, int obstacle_threshold, int no_change,
+                                  unsigned flags, unsigned long long *changed);
+/* epic_hip_set_occupancy_2d_gpu bracketing its kernel with HIP events on the library's stream: *kernel_ms = the device time of
+ * the ingestion kernel alone (not the copy of the image, not the rebuild of the fused masks; 0 in multi-device mode).  For
+ * tools/bench_occupancy.py: the stream is the library's own, nothing outside can time a kernel on it. */
+int epic_hip_timed_occupancy_2d_gpu(EpicHarmonicT *h, const void *occ, int obstacle_threshold, int no_change,
+                                    unsigned flags, unsigned long long *changed, float *kernel_ms);
+int epic_hip_reset_free_cells_2d_cpu(EpicHarmonicT *h);
+int epic_hip_reset_free_cells_2d_gpu(EpicHarmonicT *h);
+
 /* Diagnostic: the number of tiles the next iteration will recompute and the number of tiles (both 0 when tracking is
  * off).  Synchronises the stream and copies the list counters to the host. */
 int epic_hip_activity_stats(EpicHarmonicT *harmonic, unsigned long long *active_tiles, unsigned long long *tiles);
