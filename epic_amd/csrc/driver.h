@@ -29,6 +29,8 @@
 // All of it is host code: tests/test_host_driver_faults.py compiles these files unchanged with g++ against a fake HIP runtime.
 //   occupancy_driver.hip the dense occupancy ingestion of include/epic_hip.h (a map message's bytes onto the resident state); not one of
 //                        the driver_* units above: it calls launchers the fake runtime does not know
+//   field3d_driver.hip   streamlines and sparse edits on a resident 3-D field (epic_hip_*_3d_gpu); kept out of the driver_* units for
+//                        the same reason
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>

@@ -239,4 +239,19 @@ hipError_t launch_pack_mask_3d(const uint32_t *locked, int m0, int m1, int m2, i
                                hipStream_t stream);
 inline size_t mask_words_3d(int m0, int m1, int pitch) { return (size_t)m0 * (size_t)m1 * (size_t)(pitch / 32); }
 
+// ---- consumers and edits of the resident 3-D field (field_3d.hip); called from field3d_driver.hip only ----------------
+// The 3-D masks are the 2-D lane masks over the m0 * m1 rows of m2 cells: word and bit of cell (x0, x1, x2) are
+// mask_word_2d(x0 * m1 + x1, x2, pitch) and mask_bit_2d(x2).
+// Streamlines, one lane per start point.  d_starts: n_paths (x, y, z) triples, x along m2, y along m1, z along m0; d_pts: n_paths x
+// 3 * max_points floats; d_k: points per path (0 on failure); d_rc: EPIC_* code per path.
+hipError_t launch_follow_paths_3d(const float *u, const uint32_t *maskw, int m0, int m1, int m2, int pitch, unsigned n_paths,
+                                  const float *d_starts, float step, float cd, unsigned max_points, float *d_pts, unsigned *d_k,
+                                  int *d_rc, hipStream_t stream);
+// d_pts as above (rows of `row` floats) -> d_packed: path i's 3 * d_k[i] floats at d_packed + 3 * d_offset[i]; d_offset = the running sum of k
+hipError_t launch_pack_paths_3d(const float *d_pts, size_t row, unsigned n_paths, const unsigned *d_k, const unsigned long long *d_offset,
+                                float *d_packed, hipStream_t stream);
+// Sparse edits: v = k (x, y, z) triples, types = k EPIC_CELL_TYPE_*; no cell may appear twice in one list.
+hipError_t launch_set_cells_3d(float *u, uint32_t *maskw, int m0, int m1, int m2, int pitch, unsigned k, const unsigned *v,
+                               const unsigned *types, hipStream_t stream);
+
 }  // namespace epic_hip

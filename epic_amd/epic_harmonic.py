@@ -134,6 +134,18 @@ _SIGNATURES = {
                                       ct.POINTER(ct.c_int), ct.POINTER(ct.c_float)),
     "epic_hip_compute_path_2d_gpu": (_H, ct.c_float, ct.c_float, ct.c_float, ct.c_float, ct.c_uint, _UP,
                                      ct.POINTER(ct.POINTER(ct.c_float))),
+    # 3-D fields: points, way-points and cell lists are (x, y, z) triples
+    "epic_hip_compute_potential_3d_cpu": (_H, ct.c_float, ct.c_float, ct.c_float, ct.POINTER(ct.c_float)),
+    "epic_hip_compute_gradient_3d_cpu": (_H, ct.c_float, ct.c_float, ct.c_float, ct.c_float, ct.POINTER(ct.c_float),
+                                         ct.POINTER(ct.c_float), ct.POINTER(ct.c_float)),
+    "epic_hip_compute_path_3d_cpu": (_H, ct.c_float, ct.c_float, ct.c_float, ct.c_float, ct.c_float, ct.c_uint, _UP,
+                                     ct.POINTER(ct.POINTER(ct.c_float))),
+    "epic_hip_set_cells_3d_cpu": (_H, ct.c_uint, _UP, _UP),
+    "epic_hip_compute_paths_3d_gpu": (_H, ct.c_uint, ct.POINTER(ct.c_float), ct.c_float, ct.c_float, ct.c_uint, _UP,
+                                      ct.POINTER(ct.c_int), ct.POINTER(ct.c_float)),
+    "epic_hip_compute_path_3d_gpu": (_H, ct.c_float, ct.c_float, ct.c_float, ct.c_float, ct.c_float, ct.c_uint, _UP,
+                                     ct.POINTER(ct.POINTER(ct.c_float))),
+    "epic_hip_set_cells_3d_gpu": (_H, ct.c_uint, _UP, _UP),
     "epic_hip_set_occupancy_2d_cpu": (_H, ct.c_void_p, ct.c_int, ct.c_int, ct.c_uint, ct.POINTER(ct.c_ulonglong)),
     "epic_hip_set_occupancy_2d_gpu": (_H, ct.c_void_p, ct.c_int, ct.c_int, ct.c_uint, ct.POINTER(ct.c_ulonglong)),
     "epic_hip_timed_occupancy_2d_gpu": (_H, ct.c_void_p, ct.c_int, ct.c_int, ct.c_uint, ct.POINTER(ct.c_ulonglong),

@@ -142,6 +142,77 @@ class Harmonic(eh.EpicHarmonic):
                 if rc != 0:
                     raise RuntimeError("epic_amd: %s failed with code %d" % (variant.__name__, rc))
 
+    # -- consumers and sparse edits, 2-D and 3-D ------------------------------------------------------------
+    def compute_paths(self, starts, step_size, cd_precision, max_length, process='gpu'):
+        """Streamlines from ``starts``, an (N, n) float32 array of points in cell units -- (x, y) for a 2-D grid, (x, y, z) for
+        a 3-D one (x along the last axis of m; include/epic_hip.h).  ``process``: 'gpu' walks the device-resident field in one
+        batched call (epic_hip_compute_paths_2d_gpu / _3d_gpu), 'cpu' walks the host arrays one start at a time
+        (harmonic_compute_path_2d_cpu / epic_hip_compute_path_3d_cpu).  Returns ``(paths, codes)``: a list of N float32 arrays
+        of shape (k_i, n) -- empty where the walk failed -- and an int32 array of the N per-path codes."""
+        if process not in ('gpu', 'cpu'):
+            raise ValueError("process must be 'gpu' or 'cpu'")
+        n = int(self.n)
+        if n not in (2, 3):
+            raise ValueError("streamlines exist for 2-D and 3-D grids, not n = %d" % n)
+        starts = np.ascontiguousarray(np.asarray(starts, dtype=np.float32))
+        if starts.ndim != 2 or starts.shape[1] != n:
+            raise ValueError("starts must have shape (N, %d)" % n)
+        count = starts.shape[0]
+        codes = np.zeros(count, dtype=np.int32)
+        if count == 0:
+            return [], codes
+        PF = ct.POINTER(ct.c_float)
+        if process == 'gpu':
+            batch = eh._epic.epic_hip_compute_paths_2d_gpu if n == 2 else eh._epic.epic_hip_compute_paths_3d_gpu
+            points = (2 * int(max_length) & 0xffffffff) // 2      # the walk's own bound: an unsigned product
+            k = np.zeros(count, dtype=np.uint32)
+            out = np.empty((count, max(n * points, 1)), dtype=np.float32)
+            rc = batch(self, count, starts.ctypes.data_as(PF), float(step_size), float(cd_precision), int(max_length),
+                       k.ctypes.data_as(ct.POINTER(ct.c_uint)), codes.ctypes.data_as(ct.POINTER(ct.c_int)), out.ctypes.data_as(PF))
+            if rc != 0:
+                raise RuntimeError("epic_amd: %s failed with code %d" % (batch.__name__, rc))
+            return [out[i, :n * int(k[i])].reshape(-1, n).copy() for i in range(count)], codes
+        walk = eh._epic.harmonic_compute_path_2d_cpu if n == 2 else eh._epic.epic_hip_compute_path_3d_cpu
+        paths = []
+        for i in range(count):
+            k, raw = ct.c_uint(0), PF()
+            codes[i] = walk(self, *[float(c) for c in starts[i]], float(step_size), float(cd_precision), int(max_length),
+                            ct.byref(k), ct.byref(raw))
+            if codes[i] == 0:
+                paths.append(np.ctypeslib.as_array(raw, shape=(n * k.value,)).reshape(-1, n).copy())
+                eh._epic.harmonic_free_path_cpu(ct.byref(raw))
+            else:
+                paths.append(np.empty((0, n), dtype=np.float32))
+        return paths, codes
+
+    def set_cells(self, v, types, process='both', numThreads=1024):
+        """Sparse edits: ``v`` is a (k, n) array of cells -- (x, y) or (x, y, z), x along the last axis of m -- and ``types`` k
+        EPIC_CELL_TYPE_* values.  ``process`` as in ``set_occupancy``: 'cpu' edits the host arrays, 'gpu' the device-resident
+        state, 'both' the host arrays and then the device state (harmonic_utilities_set_cells_2d_cpu / _gpu for a 2-D grid,
+        epic_hip_set_cells_3d_cpu / _gpu for a 3-D one).  A list for the device must not name a cell twice."""
+        if process not in ('gpu', 'cpu', 'both'):
+            raise ValueError("process must be 'gpu', 'cpu' or 'both'")
+        n = int(self.n)
+        if n not in (2, 3):
+            raise ValueError("sparse edits exist for 2-D and 3-D grids, not n = %d" % n)
+        v = np.ascontiguousarray(np.asarray(v, dtype=np.uint32))
+        types = np.ascontiguousarray(np.asarray(types, dtype=np.uint32)).reshape(-1)
+        if v.ndim != 2 or v.shape[1] != n or v.shape[0] != types.size:
+            raise ValueError("v must have shape (k, %d) and types k entries" % n)
+        UP = ct.POINTER(ct.c_uint)
+        args = (int(types.size), v.ctypes.data_as(UP), types.ctypes.data_as(UP))
+        if n == 2:
+            variants = ((eh._epic.harmonic_utilities_set_cells_2d_cpu, (self,) + args, ('cpu', 'both')),
+                        (eh._epic.harmonic_utilities_set_cells_2d_gpu, (self, int(numThreads)) + args, ('gpu', 'both')))
+        else:
+            variants = ((eh._epic.epic_hip_set_cells_3d_cpu, (self,) + args, ('cpu', 'both')),
+                        (eh._epic.epic_hip_set_cells_3d_gpu, (self,) + args, ('gpu', 'both')))
+        for variant, call_args, wanted in variants:
+            if process in wanted:
+                rc = variant(*call_args)
+                if rc != 0:
+                    raise RuntimeError("epic_amd: %s failed with code %d" % (variant.__name__, rc))
+
     def __str__(self):
         s = "n: %d\nm: %s\nepsilon: %g\ndelta: %g\nnumIterationsToStaggerCheck: %d\ncurrentIteration: %d\n" % (
             self.n, list(self.shape), self.epsilon, self.delta, self.numIterationsToStaggerCheck,

@@ -134,6 +134,47 @@ int epic_hip_compute_paths_2d_gpu(EpicHarmonicT *harmonic, unsigned int n_paths,
 int epic_hip_compute_path_2d_gpu(EpicHarmonicT *harmonic, float x, float y, float stepSize, float cdPrecision,
                                  unsigned int maxLength, unsigned int *k, float **path);
 
+/* ---- 3-D fields: potential, gradient, streamlines and sparse edits ---------------------------------------------------
+ * The reference relaxes n-D grids but consumes and edits only 2-D ones; these close the caller's loop for n == 3.
+ * Axes: cell (x0, x1, x2) of m = {m0, m1, m2} sits at u[(x0 * m1 + x1) * m2 + x2].  A point is (x, y, z) in cell units, x along
+ * m[2] (columns), y along m[1] (rows), z along m[0] (planes): the 2-D convention (x along m[1], y along m[0]) with z added as
+ * the slowest axis.  Way-points and cell lists are (x, y, z) triples in this order.
+ * The rule is the reference's 2-D one (libepic/src/harmonic/harmonic_path_cpu.cpp:41-232) generalised operation by operation,
+ * the third axis always the last operand: trilinear = (1 - gamma) * front + gamma * back with front / back the 2-D bilinear on
+ * planes z0 / z1; six samples at +-cdPrecision in the order x-, x+, y-, y+, z-, z+; the norm and the stuck distance are
+ * three-term sums in double, left to right.  A field that is constant along z, walked from an integer z with cdPrecision 0.5,
+ * therefore reproduces harmonic_compute_path_2d_cpu bit for bit.  Codes and stderr texts are the 2-D ones under the new names;
+ * a point that leaves the grid ends the walk.
+ *   epic_hip_compute_path_3d_cpu  *path must be NULL, receives a new[] array of 3 * *k floats (release with harmonic_free_path_cpu).
+ *   epic_hip_set_cells_3d_cpu     harmonic_utilities_set_cells_2d_cpu on k triples: same types, values, warnings and skipping.
+ * EPIC_ERROR_INVALID_DATA: a null harmonic, m, u, locked or output pointer, n != 3, (set_cells) k == 0.
+ * The _gpu calls work on the device-resident state of a 3-D Harmonic and have the contracts of their 2-D counterparts
+ * (epic_hip_compute_paths_2d_gpu, epic_hip_compute_path_2d_gpu, harmonic_utilities_set_cells_2d_gpu): ordering points, host
+ * pointers only, the same codes for the same failing steps.
+ *   starts  n_paths (x, y, z) triples;  k / rc  n_paths entries (k = 0 unless rc is EPIC_SUCCESS);
+ *   paths   n_paths rows of 3 * maxLength floats, row i holding k[i] triples -- bit-identical to epic_hip_compute_path_3d_cpu on
+ *           the same field.
+ * Border rule: the device mask treats every face of the grid as locked (a precondition of the solver), so a device walk ends on a
+ * face cell and epic_hip_set_cells_3d_gpu leaves a face cell locked whatever type it is given (its value is still written).
+ * Duplicate cells: the edits of one list are applied concurrently; a list must not name a cell twice (the result for that cell
+ * would be either entry's).  Out-of-area entries and invalid types are skipped, silently on the device.
+ * epic_hip_set_cells_3d_gpu edits the device state only (the current u buffer and the masks), synchronises, and makes the next two
+ * iterations of a tracked relaxation run every tile.
+ * Multi-device mode (EPIC_HIP_DEVICES): plane-slab versions are not built.  All three _gpu calls return EPIC_ERROR_INVALID_DATA
+ * with a message naming the host route: harmonic_get_potential_values_gpu + epic_hip_compute_path_3d_cpu for paths,
+ * epic_hip_set_cells_3d_cpu + harmonic_update_model_gpu for edits. */
+int epic_hip_compute_potential_3d_cpu(EpicHarmonicT *h, float x, float y, float z, float *potential);
+int epic_hip_compute_gradient_3d_cpu(EpicHarmonicT *h, float x, float y, float z, float cdPrecision, float *gx, float *gy,
+                                     float *gz);
+int epic_hip_compute_path_3d_cpu(EpicHarmonicT *h, float x, float y, float z, float stepSize, float cdPrecision,
+                                 unsigned int maxLength, unsigned int *k, float **path);
+int epic_hip_set_cells_3d_cpu(EpicHarmonicT *h, unsigned int k, const unsigned int *v, const unsigned int *types);
+int epic_hip_compute_paths_3d_gpu(EpicHarmonicT *h, unsigned int n_paths, const float *starts, float stepSize, float cdPrecision,
+                                  unsigned int maxLength, unsigned int *k, int *rc, float *paths);
+int epic_hip_compute_path_3d_gpu(EpicHarmonicT *h, float x, float y, float z, float stepSize, float cdPrecision,
+                                 unsigned int maxLength, unsigned int *k, float **path);
+int epic_hip_set_cells_3d_gpu(EpicHarmonicT *h, unsigned int k, const unsigned int *v, const unsigned int *types);
+
 /* ---- dense occupancy-grid ingestion (2-D) -------------------------------------------------------------------------
  * A map message applied where the state lives.  The reference's callers expand a message into a list of (x, y) pairs and a
  * list of types with one entry per interior cell and hand both to harmonic_utilities_set_cells_2d_cpu / _gpu
