@@ -225,6 +225,27 @@ def test_set_cells_3d_cpu(capfd):
     assert "Error[epic_hip_set_cells_3d_cpu]: Invalid data." in capfd.readouterr().err
 
 
+# Start points whose x is no index at all.  to_index is (unsigned)(long long)v: for NaN, +-inf and |v| >= 2^63 the conversion is undefined
+# in C++ and x86-64 resolves it to 0x8000000000000000, a low word of 0 -- column 0, like 2^32 and -2^32, whose low words are 0 by
+# arithmetic, and like -0.75 .. -0.49, which truncate to 0 after the + 0.5.  3e9 fits and lies outside the grid.  With FACE_GOAL, a cell of
+# the x == 0 face, made a goal, column 0 is a usable start on which the walk ends at once (one point: EPIC_ERROR_INVALID_PATH);
+# tests/test_gpu_field_states.py holds the device to the same codes.
+FACE_GOAL = (0, 9, 5)
+WILD_X = [float("nan"), float("inf"), float("-inf"), 1e20, -1e20, 9.3e18, 2.0 ** 32, -2.0 ** 32, 3e9, -0.75, -0.5, -0.49]
+WILD_X_CODES = [13, 13, 13, 13, 13, 13, 13, 13, 10, 13, 13, 13]
+
+
+def test_start_points_that_are_no_index_land_in_column_zero(relaxed):
+    m, u, locked = relaxed
+    h = Harmonic()
+    h.set_grid(m, u, locked)
+    _, y, z = FACE_GOAL
+    assert [walk3(h, x, float(y), float(z), 0.2, 0.5, 300)[0] for x in WILD_X] == [10] * len(WILD_X)   # column 0 is an obstacle: the border
+    v, t = np.array([FACE_GOAL], dtype=np.uint32), np.array([eh.EPIC_CELL_TYPE_GOAL], dtype=np.uint32)
+    assert E.epic_hip_set_cells_3d_cpu(h, 1, v.ctypes.data_as(UP), t.ctypes.data_as(UP)) == 0
+    assert [walk3(h, x, float(y), float(z), 0.2, 0.5, 300)[0] for x in WILD_X] == WILD_X_CODES
+
+
 def test_python_methods_on_the_host(relaxed):
     """Harmonic.compute_paths(process='cpu') and Harmonic.set_cells(process='cpu') against the ctypes calls, n == 2 and n == 3."""
     m, u, locked = relaxed
