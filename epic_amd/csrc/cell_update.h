@@ -21,7 +21,9 @@
 //      (tools/probe_transcendentals.hip, profiles/r01_probe_transcendentals.txt), which moved the converged field
 //      of the 256x256 reference map by 2e-5 (relative) -- outside the 1e-5 parity bar.
 //
-//  kMathFast  v_exp_f32 / v_log_f32 with f32 base changes.  ~2.5x less ALU; for well-conditioned maps only.
+//  kMathFast  v_exp_f32 / v_log_f32 with f32 base changes.  ~2.5x less ALU; for well-conditioned maps only.  The WHOLE update against
+//      its exact value (tests/test_gpu_update_accuracy.py; units = f32 spacings at max(|t|, |u'|)): biased against precise by -0.25..-0.33
+//      units in 2-D and -0.27..-0.62 in 3-D where |u| <~ 1 and next to a goal, -0.03..-0.15 at |u| ~ 5, nothing measurable from |u| ~ 40 on.
 //
 //  kMathTol   (further down: "tol math") does not evaluate e() per neighbour at all: every cell's potential is split once into
 //      e^u = q 2^n and the cells it is a neighbour of share the pair; its logarithm is its own (TolLn: 256 intervals per
@@ -318,7 +320,10 @@ template <int BINADES> struct TolLn {
 //     t = mx + l,   u' = (float)((double)t - ln 2n)                                  as the reference
 // The rounding stages of the reference -- f32 sum, l to f32, mx + l to f32, the f64 subtraction to f32 -- are all there;
 // what differs is the noise inside the sum (the terms carry the rounding of q instead of the rounding of expf, ~4e-8
-// relative either way, zero mean).  The terms are never formed by subtracting the maximum first, so Jacobi's two
+// relative either way).  Its mean is small, not zero: one update against its exact value (tests/test_update_accuracy_cpu.py, DESIGN.md
+// section 2) puts tol within 0.04 units of the reference's sequence in every regime (bound: 0.1) and up to 1.125 units above its
+// largest error; the largest paired bias, +0.03..+0.04 where the lesser neighbours lie 15-18 below the largest, is the reference's
+// sum 1 + tiny losing terms to the ulp of 1.0 that q_mx + tiny with q_mx < 1 keeps.  The terms are never formed by subtracting the maximum first, so Jacobi's two
 // interleaved chains see the same term for the same neighbour value; on the reference's maps Jacobi, red-black and any
 // tiling end in ONE fixed point with max |du| = 0 exactly, which is what lets the reference's absolute termination test
 // fire under Jacobi (round 1's per-neighbour double-float mode ended in two fixed points one ulp apart on umass).

@@ -94,7 +94,9 @@ int epic_hip_set_rows_per_task(EpicHarmonicT *harmonic, unsigned int rows_per_ta
  *                        on every map and grid under test, 1.4e-6 on the ill-conditioned umass.png (the tol iteration
  *                        alone: 1.6e-5 there).  ~1.3x faster per sweep than precise, ~1.75x where pairs of
  *                        iterations run as one fused pass (epic_hip_iterations_per_pass); the benchmarked mode;
- *   1 fast               v_exp_f32 / v_log_f32: biased, ~1e-4 relative drift on ill-conditioned maps; no parity claim;
+ *   1 fast               v_exp_f32 / v_log_f32: biased (one update: -0.25 to -0.6 f32 spacings against precise where |u| <~ 1
+ *                        and next to a goal, nothing from |u| ~ 40 on), ~1e-4 relative drift on ill-conditioned maps; no
+ *                        parity claim;
  *   2 traffic            diagnostic: same loads/stores, trivial arithmetic (2-D only).
  * (3 was round 1's df32 mode, removed: EPIC_ERROR_INVALID_DATA.) */
 int epic_hip_set_math_mode(EpicHarmonicT *harmonic, int mode);
