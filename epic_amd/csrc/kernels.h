@@ -254,4 +254,18 @@ hipError_t launch_pack_paths_3d(const float *d_pts, size_t row, unsigned n_paths
 hipError_t launch_set_cells_3d(float *u, uint32_t *maskw, int m0, int m1, int m2, int pitch, unsigned k, const unsigned *v,
                                const unsigned *types, hipStream_t stream);
 
+// ---- dense occupancy ingestion into a region of a 2-D or 3-D field (occupancy_region.hip) -----------------------------------
+// The box origin[i] .. origin[i] + extent[i] - 1 of a field of m0 x m1 planes-by-rows of `cols` cells (2-D: m0 = 1, origin[0] = 0,
+// extent[0] = 1; the entries are in the order of m, slowest axis first) and its bytes d_occ, extent[0] * extent[1] rows of
+// extent[2] bytes, unpitched.  The rule, d_changed and the counters are launch_occupancy_2d's; only the (row, strip) pairs the box
+// touches are launched, and a cell is decided only inside the box, off the faces (2-D: off the border).  The caller has checked
+// that the box lies inside the grid.  The fused masks of a 2-D field are NOT rebuilt.  Called from occupancy_driver.hip only.
+struct OccRegion {
+    int m0, m1, cols;      // the grid; 2-D: m0 == 1, m1 = rows
+    int origin[3], extent[3];
+    bool faces0;           // the first axis has faces (3-D); false: 2-D
+};
+hipError_t launch_occupancy_region(float *u, uint32_t *maskw, const unsigned char *d_occ, const OccRegion &region, int pitch,
+                                   int obstacle_threshold, int no_change, unsigned flags, unsigned long long *d_changed, hipStream_t stream);
+
 }  // namespace epic_hip

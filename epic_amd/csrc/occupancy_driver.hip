@@ -12,6 +12,11 @@
 // takes on slabs.  The rule needs the cells as the devices hold them, so the field and the lock bits of the owned rows are read
 // back first.  That is a whole field over the bus per message: the mode keeps its results bit-identical to one device, not the
 // dense route's cost.
+//
+// The region forms (epic_hip_set_occupancy_region_gpu, epic_hip_timed_occupancy_region_gpu, epic_hip_reset_free_cells_3d_gpu) follow
+// the same sequence on 2-D and 3-D fields with the launcher of occupancy_region.hip: only the region's bytes are copied.  The 3-D
+// sweeps derive nothing from the masks, so a 3-D edit rebuilds nothing.  In multi-device mode a 2-D region takes the list route
+// above, restricted to the window; a 3-D field lives in plane slabs there, for which no edit is built: the calls name the host route.
 #include "driver.h"
 #include "occupancy_rule.h"
 
@@ -50,9 +55,9 @@ int multi_snapshot(Harmonic *h, Ctx *c, std::vector<float> &u, std::vector<unsig
     return EPIC_SUCCESS;
 }
 
-// occ == nullptr: reset_free_cells
+// occ == nullptr: reset_free_cells.  win (may be null: the grid): {y0, x0, height, width} of the window `occ` holds, unpitched.
 int multi_dense_edit(Harmonic *h, Ctx *c, const unsigned char *occ, int obstacle_threshold, int no_change, unsigned flags,
-                     unsigned long long *changed, const char *fn)
+                     unsigned long long *changed, const char *fn, const size_t *win = nullptr)
 {
     std::vector<float> u;
     std::vector<unsigned char> locked;
@@ -61,12 +66,13 @@ int multi_dense_edit(Harmonic *h, Ctx *c, const unsigned char *occ, int obstacle
     std::vector<unsigned> v, types;
     unsigned long long count = 0;
     const size_t cols = (size_t)c->cols;
-    for (size_t y = 1; y + 1 < (size_t)c->rows; y++)
-        for (size_t x = 1; x + 1 < cols; x++) {
+    const size_t y0 = win ? win[0] : 0, x0 = win ? win[1] : 0, height = win ? win[2] : (size_t)c->rows, width = win ? win[3] : cols;
+    for (size_t y = std::max<size_t>(y0, 1); y < y0 + height && y + 1 < (size_t)c->rows; y++)
+        for (size_t x = std::max<size_t>(x0, 1); x < x0 + width && x + 1 < cols; x++) {
             const size_t cell = y * cols + x;
             const bool was_locked = locked[cell] != 0;
             epic_hip::OccCell after = {u[cell], was_locked, false};
-            if (occ) after = epic_hip::occupancy_cell(occ[cell], u[cell], was_locked, obstacle_threshold, no_change, flags);
+            if (occ) after = epic_hip::occupancy_cell(occ[(y - y0) * width + (x - x0)], u[cell], was_locked, obstacle_threshold, no_change, flags);
             else if (!was_locked) after.u = (float)EPIC_LOG_SPACE_FREE;
             count += epic_hip::occupancy_changed(u[cell], was_locked, after);
             if (after.locked == was_locked && epic_hip::occupancy_float_bits(after.u) == epic_hip::occupancy_float_bits(u[cell])) continue;
@@ -87,25 +93,14 @@ int multi_dense_edit(Harmonic *h, Ctx *c, const unsigned char *occ, int obstacle
     return multi_set_cells(c, (unsigned)types.size(), v.data(), types.data(), fn);
 }
 
-// kernel_ms (may be null): the device time of occupancy_2d_kernel alone, between two events on the context's stream
-int set_occupancy(Harmonic *harmonic, const void *occ, int obstacle_threshold, int no_change, unsigned flags, unsigned long long *changed,
-                  float *kernel_ms, const char *fn)
+// The sequence both dense calls share, behind the ordering point: one temporary -- the counters of `changed` (kernels.h: kOccCounters
+// words in lines of their own) and behind them the `bytes` bytes of the image or the region, copied as they are (staging an image with
+// rows padded to the field's pitch was measured and gained nothing: profiles/occupancy_ingest.txt) --, launch(d_occ, d_changed), in 2-D
+// the fused masks, the counters back, synchronise, free, and force_all unless KEEP_FREE is set and nothing changed.
+// kernel_ms (may be null): the device time of the ingestion kernel alone, between two events on the context's stream
+template <class Launch>
+int staged_edit(Ctx *c, const void *occ, size_t bytes, unsigned flags, unsigned long long *changed, float *kernel_ms, const char *fn, Launch launch)
 {
-    Ctx *c = valid_host_side(harmonic) && occ != nullptr ? find_ctx(harmonic) : nullptr;
-    if (c == nullptr || !ready(harmonic, c) || c->n != 2) {
-        report(fn, "Invalid data.");
-        return EPIC_ERROR_INVALID_DATA;
-    }
-    {
-        const int frc = flush_pending(harmonic, c, fn);   // the iterations counted so far act on the cells as they were
-        if (frc != EPIC_SUCCESS) return frc;
-    }
-    if (kernel_ms) *kernel_ms = 0.0f;
-    if (c->multi()) return multi_dense_edit(harmonic, c, static_cast<const unsigned char *>(occ), obstacle_threshold, no_change, flags, changed, fn);
-
-    // one temporary: the counters of `changed` (kernels.h: kOccCounters words in lines of their own) and behind them the image, copied
-    // as it is (staging it with rows padded to the field's pitch was measured and gained nothing: profiles/occupancy_ingest.txt)
-    const size_t rows = (size_t)c->rows, cols = (size_t)c->cols;
     const size_t slot = epic_hip::kOccCounterBytes;
     unsigned char *tmp = nullptr;
     unsigned long long count = 0;
@@ -117,7 +112,7 @@ int set_occupancy(Harmonic *harmonic, const void *occ, int obstacle_threshold, i
         (void)hipGetLastError();
         report(fn, "Failed to create the timing events.");
         rc = EPIC_ERROR_DEVICE_MALLOC;
-    } else if (hipMalloc((void **)&tmp, slot + rows * cols) != hipSuccess) {
+    } else if (hipMalloc((void **)&tmp, slot + bytes) != hipSuccess) {
         (void)hipGetLastError();
         report(fn, "Failed to allocate device-side memory for the occupancy image.");
         rc = EPIC_ERROR_DEVICE_MALLOC;
@@ -125,14 +120,13 @@ int set_occupancy(Harmonic *harmonic, const void *occ, int obstacle_threshold, i
         unsigned long long *d_changed = reinterpret_cast<unsigned long long *>(tmp);
         unsigned char *d_occ = tmp + slot;
         if (hipMemsetAsync(d_changed, 0, slot, c->stream) != hipSuccess ||
-            hipMemcpyAsync(d_occ, occ, rows * cols, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+            hipMemcpyAsync(d_occ, occ, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
             report(fn, "Failed to copy memory from host to device for the occupancy image.");
             rc = EPIC_ERROR_MEMCPY_TO_DEVICE;
         } else if ((kernel_ms && hipEventRecord(ev[0], c->stream) != hipSuccess) ||
-                   epic_hip::launch_occupancy_2d(c->buf[c->cur], c->maskw, d_occ, cols, c->rows, c->cols, c->pitch, obstacle_threshold,
-                                                 no_change, flags, d_changed, c->stream) != hipSuccess ||
+                   launch(d_occ, d_changed) != hipSuccess ||
                    (kernel_ms && hipEventRecord(ev[1], c->stream) != hipSuccess) ||
-                   epic_hip::launch_fuse_masks_2d(c->maskw, c->rows, c->pitch, c->maskf(), c->stream) != hipSuccess) {
+                   (c->n == 2 && epic_hip::launch_fuse_masks_2d(c->maskw, c->rows, c->pitch, c->maskf(), c->stream) != hipSuccess)) {
             report(fn, "Failed to execute the 'set occupancy' kernel.");
             rc = EPIC_ERROR_KERNEL_EXECUTION;
         } else if (hipMemcpyAsync(counters.data(), d_changed, slot, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
@@ -158,6 +152,73 @@ int set_occupancy(Harmonic *harmonic, const void *occ, int obstacle_threshold, i
     }
     if (!untouched) force_all(c);   // cells and mask bits changed under the work lists (or a failure left that open)
     return rc;
+}
+
+int set_occupancy(Harmonic *harmonic, const void *occ, int obstacle_threshold, int no_change, unsigned flags, unsigned long long *changed,
+                  float *kernel_ms, const char *fn)
+{
+    Ctx *c = valid_host_side(harmonic) && occ != nullptr ? find_ctx(harmonic) : nullptr;
+    if (c == nullptr || !ready(harmonic, c) || c->n != 2) {
+        report(fn, "Invalid data.");
+        return EPIC_ERROR_INVALID_DATA;
+    }
+    {
+        const int frc = flush_pending(harmonic, c, fn);   // the iterations counted so far act on the cells as they were
+        if (frc != EPIC_SUCCESS) return frc;
+    }
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (c->multi()) return multi_dense_edit(harmonic, c, static_cast<const unsigned char *>(occ), obstacle_threshold, no_change, flags, changed, fn);
+
+    const size_t cols = (size_t)c->cols;
+    return staged_edit(c, occ, (size_t)c->rows * cols, flags, changed, kernel_ms, fn, [&](const unsigned char *d_occ, unsigned long long *d_changed) {
+        return epic_hip::launch_occupancy_2d(c->buf[c->cur], c->maskw, d_occ, cols, c->rows, c->cols, c->pitch, obstacle_threshold, no_change, flags,
+                                             d_changed, c->stream);
+    });
+}
+
+const char *kMulti3dRegion = "Invalid data (not available in multi-device mode: use epic_hip_set_occupancy_region_cpu and harmonic_update_model_gpu).";
+const char *kMulti3dReset = "Invalid data (not available in multi-device mode: use epic_hip_reset_free_cells_3d_cpu and harmonic_update_model_gpu).";
+
+// The region form, n in {2, 3}: set_occupancy's ordering point and staged_edit, with only the region's bytes over the bus and only
+// the region's rows and strips under the kernel (occupancy_region.hip).
+int set_occupancy_region(Harmonic *harmonic, const void *occ, const unsigned *origin, const unsigned *extent, int obstacle_threshold,
+                         int no_change, unsigned flags, unsigned long long *changed, float *kernel_ms, const char *fn)
+{
+    size_t m[3], o[3], e[3];
+    const bool host_ok = harmonic != nullptr && harmonic->m != nullptr && harmonic->u != nullptr && harmonic->locked != nullptr &&
+                         occ != nullptr && epic_hip::occupancy_region(harmonic->n, harmonic->m, origin, extent, m, o, e);
+    Ctx *c = host_ok ? find_ctx(harmonic) : nullptr;
+    if (c == nullptr || !ready(harmonic, c) || c->n != (int)harmonic->n || !same_dims(harmonic, c)) {
+        report(fn, "Invalid data.");
+        return EPIC_ERROR_INVALID_DATA;
+    }
+    if (c->n == 3 && c->multi()) {  // plane slabs: edit the host arrays and upload them again
+        report(fn, kMulti3dRegion);
+        return EPIC_ERROR_INVALID_DATA;
+    }
+    {
+        const int frc = flush_pending(harmonic, c, fn);   // the iterations counted so far act on the cells as they were
+        if (frc != EPIC_SUCCESS) return frc;
+    }
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (c->multi()) {
+        const size_t win[4] = {o[1], o[2], e[1], e[2]};
+        return multi_dense_edit(harmonic, c, static_cast<const unsigned char *>(occ), obstacle_threshold, no_change, flags, changed, fn, win);
+    }
+
+    epic_hip::OccRegion region;
+    region.m0 = (int)m[0];
+    region.m1 = (int)m[1];
+    region.cols = (int)m[2];
+    for (int a = 0; a < 3; a++) {
+        region.origin[a] = (int)o[a];
+        region.extent[a] = (int)e[a];
+    }
+    region.faces0 = c->n == 3;
+    return staged_edit(c, occ, e[0] * e[1] * e[2], flags, changed, kernel_ms, fn, [&](const unsigned char *d_occ, unsigned long long *d_changed) {
+        return epic_hip::launch_occupancy_region(c->buf[c->cur], c->maskw, d_occ, region, c->pitch, obstacle_threshold, no_change, flags, d_changed,
+                                                 c->stream);
+    });
 }
 
 }  // namespace
@@ -198,6 +259,56 @@ int epic_hip_reset_free_cells_2d_gpu(Harmonic *harmonic)
         if (frc != EPIC_SUCCESS) return frc;
     }
     if (c->multi()) return multi_dense_edit(harmonic, c, nullptr, 0, 0, 0, nullptr, fn);
+    int rc = EPIC_SUCCESS;
+    force_all(c);   // values change under the work lists
+    if (epic_hip::launch_reset_free_cells_2d(c->buf[c->cur], c->maskw, c->rows, c->cols, c->pitch, c->stream) != hipSuccess) {
+        report(fn, "Failed to execute the 'reset free cells' kernel.");
+        rc = EPIC_ERROR_KERNEL_EXECUTION;
+    }
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == EPIC_SUCCESS) {
+        report(fn, "Failed to synchronize the device after 'reset free cells' kernel.");
+        rc = EPIC_ERROR_DEVICE_SYNCHRONIZE;
+    }
+    return rc;
+}
+
+int epic_hip_set_occupancy_region_gpu(Harmonic *harmonic, const void *occ, const unsigned int *origin, const unsigned int *extent,
+                                      int obstacle_threshold, int no_change, unsigned flags, unsigned long long *changed)
+{
+    return set_occupancy_region(harmonic, occ, origin, extent, obstacle_threshold, no_change, flags, changed, nullptr,
+                                "epic_hip_set_occupancy_region_gpu");
+}
+
+int epic_hip_timed_occupancy_region_gpu(Harmonic *harmonic, const void *occ, const unsigned int *origin, const unsigned int *extent,
+                                        int obstacle_threshold, int no_change, unsigned flags, unsigned long long *changed, float *kernel_ms)
+{
+    static const char *fn = "epic_hip_timed_occupancy_region_gpu";
+    if (kernel_ms == nullptr) {
+        report(fn, "Invalid data.");
+        return EPIC_ERROR_INVALID_DATA;
+    }
+    return set_occupancy_region(harmonic, occ, origin, extent, obstacle_threshold, no_change, flags, changed, kernel_ms, fn);
+}
+
+// unlocked cells are interior cells (the faces and the padding are locked in the masks), and the 3-D masks are the 2-D lane masks
+// over m0 * m1 rows: the 2-D kernel does the work
+int epic_hip_reset_free_cells_3d_gpu(Harmonic *harmonic)
+{
+    static const char *fn = "epic_hip_reset_free_cells_3d_gpu";
+    const bool host_ok = harmonic != nullptr && harmonic->m != nullptr && harmonic->u != nullptr && harmonic->locked != nullptr && harmonic->n == 3;
+    Ctx *c = host_ok ? find_ctx(harmonic) : nullptr;
+    if (c == nullptr || !ready(harmonic, c) || c->n != 3) {
+        report(fn, "Invalid data.");
+        return EPIC_ERROR_INVALID_DATA;
+    }
+    if (c->multi()) {
+        report(fn, kMulti3dReset);
+        return EPIC_ERROR_INVALID_DATA;
+    }
+    {
+        const int frc = flush_pending(harmonic, c, fn);
+        if (frc != EPIC_SUCCESS) return frc;
+    }
     int rc = EPIC_SUCCESS;
     force_all(c);   // values change under the work lists
     if (epic_hip::launch_reset_free_cells_2d(c->buf[c->cur], c->maskw, c->rows, c->cols, c->pitch, c->stream) != hipSuccess) {

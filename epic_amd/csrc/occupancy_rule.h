@@ -1,6 +1,6 @@
 // occupancy_rule.h -- the per-cell rule of the dense occupancy ingestion (include/epic_hip.h: epic_hip_set_occupancy_2d_*), stated
-// once for the host walk (occupancy_cpu.cpp) and the kernel (occupancy_2d.hip).  Interior cells only: the callers never hand a
-// border cell in.
+// once for the host walk (occupancy_cpu.cpp) and the kernels (occupancy_2d.hip, occupancy_region.hip).  Interior cells only: the
+// callers never hand a border cell in.
 #pragma once
 #include <string.h>
 
@@ -55,6 +55,27 @@ EPIC_OCC_HD inline unsigned occupancy_float_bits(float f)
 EPIC_OCC_HD inline bool occupancy_changed(float u, bool was_locked, const OccCell &after)
 {
     return after.locked != was_locked || (was_locked && occupancy_float_bits(after.u) != occupancy_float_bits(u));
+}
+
+// The region of epic_hip_set_occupancy_region_* as three axes, for the host walk and the driver: origin / extent have n entries in
+// the order of m (both null: the grid); a 2-D grid is one plane, {1, rows, cols}.  False: n is not 2 or 3, exactly one of the two
+// pointers is null, or the region does not lie inside the grid (extent >= 1, origin + extent <= m, tested without overflow).
+inline bool occupancy_region(unsigned n, const unsigned *m, const unsigned *origin, const unsigned *extent, size_t grid[3], size_t o[3],
+                             size_t e[3])
+{
+    if ((n != 2 && n != 3) || (origin == nullptr) != (extent == nullptr)) return false;
+    const unsigned lead = 3 - n;
+    grid[0] = 1;
+    o[0] = 0;
+    e[0] = 1;
+    for (unsigned i = 0; i < n; i++) {
+        const unsigned mi = m[i], oi = origin ? origin[i] : 0u, ei = extent ? extent[i] : mi;
+        if (ei < 1 || oi > mi || ei > mi - oi) return false;
+        grid[lead + i] = mi;
+        o[lead + i] = oi;
+        e[lead + i] = ei;
+    }
+    return true;
 }
 
 }  // namespace epic_hip

@@ -152,6 +152,13 @@ _SIGNATURES = {
                                         ct.POINTER(ct.c_float)),
     "epic_hip_reset_free_cells_2d_cpu": (_H,),
     "epic_hip_reset_free_cells_2d_gpu": (_H,),
+    # a region of a 2-D or 3-D field: origin / extent are n entries in the order of m (both None: the grid)
+    "epic_hip_set_occupancy_region_cpu": (_H, ct.c_void_p, _UP, _UP, ct.c_int, ct.c_int, ct.c_uint, ct.POINTER(ct.c_ulonglong)),
+    "epic_hip_set_occupancy_region_gpu": (_H, ct.c_void_p, _UP, _UP, ct.c_int, ct.c_int, ct.c_uint, ct.POINTER(ct.c_ulonglong)),
+    "epic_hip_timed_occupancy_region_gpu": (_H, ct.c_void_p, _UP, _UP, ct.c_int, ct.c_int, ct.c_uint, ct.POINTER(ct.c_ulonglong),
+                                            ct.POINTER(ct.c_float)),
+    "epic_hip_reset_free_cells_3d_cpu": (_H,),
+    "epic_hip_reset_free_cells_3d_gpu": (_H,),
     "epic_hip_activity_stats": (_H, ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_ulonglong)),
     "epic_hip_activity_stats2": (_H, ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_ulonglong)),
     "epic_hip_work_done": (_H, ct.POINTER(ct.c_double), ct.c_int),

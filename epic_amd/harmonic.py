@@ -108,35 +108,61 @@ class Harmonic(eh.EpicHarmonic):
 
     # -- map messages ---------------------------------------------------------------------------------------
     def set_occupancy(self, occ, obstacle_threshold=50, no_change=-2, keep_free=False, unsigned=False, over_goals=False,
-                      process='gpu'):
+                      process='gpu', origin=None):
         """Apply a map message (one byte per cell, shape m) by the rule of epic_hip_set_occupancy_2d_* (include/epic_hip.h):
         the defaults are the navigation node's /map callback; ``unsigned=True, over_goals=True, obstacle_threshold=250,
         no_change=-1`` is the nav_core plugin's costmap rule.  ``process``: 'cpu' edits the host arrays, 'gpu' the
         device-resident state, 'both' the host arrays and then the device state, as the node does.  ``keep_free``: cells
-        that stay free keep their potential (warm start).  Returns ``changed`` (of the device call for 'both')."""
+        that stay free keep their potential (warm start).  Returns ``changed`` (of the device call for 'both').
+
+        The grid may be 2-D or 3-D.  ``origin`` (n entries in the order of m, slowest axis first) makes ``occ`` a window of
+        a map or a box of voxels placed there, ``occ.shape`` being its extent (epic_hip_set_occupancy_region_*); the
+        window must lie inside the grid."""
         if process not in ('gpu', 'cpu', 'both'):
             raise ValueError("process must be 'gpu', 'cpu' or 'both'")
+        n = int(self.n)
+        if n not in (2, 3):
+            raise ValueError("map messages exist for 2-D and 3-D grids, not n = %d" % n)
         occ = np.ascontiguousarray(np.asarray(occ, dtype=np.uint8 if unsigned else np.int8))
-        if occ.size != int(np.prod(self.shape)):
-            raise ValueError("occ must have prod(m) = %d elements" % int(np.prod(self.shape)))
         flags = ((eh.EPIC_HIP_OCC_KEEP_FREE if keep_free else 0) | (eh.EPIC_HIP_OCC_UNSIGNED if unsigned else 0)
                  | (eh.EPIC_HIP_OCC_OVER_GOALS if over_goals else 0))
+        rule = (int(obstacle_threshold), int(no_change), flags)
+        if origin is None:
+            if occ.size != int(np.prod(self.shape)):
+                raise ValueError("occ must have prod(m) = %d elements" % int(np.prod(self.shape)))
+            if n == 2:
+                variants = ((eh._epic.epic_hip_set_occupancy_2d_cpu, ()), (eh._epic.epic_hip_set_occupancy_2d_gpu, ()))
+            else:
+                variants = ((eh._epic.epic_hip_set_occupancy_region_cpu, (None, None)), (eh._epic.epic_hip_set_occupancy_region_gpu, (None, None)))
+        else:
+            origin = np.ascontiguousarray(np.asarray(origin, dtype=np.uint32)).reshape(-1)
+            if occ.ndim != n or origin.size != n:
+                raise ValueError("a window needs occ with %d axes and an origin of %d entries" % (n, n))
+            extent = np.array(occ.shape, dtype=np.uint32)
+            if np.any(extent < 1) or np.any(origin.astype(np.int64) + extent > np.array(self.shape, dtype=np.int64)):
+                raise ValueError("the window must lie inside the grid")
+            UP = ct.POINTER(ct.c_uint)
+            window = (origin.ctypes.data_as(UP), extent.ctypes.data_as(UP))
+            variants = ((eh._epic.epic_hip_set_occupancy_region_cpu, window), (eh._epic.epic_hip_set_occupancy_region_gpu, window))
         changed = ct.c_ulonglong(0)
-        for variant, wanted in ((eh._epic.epic_hip_set_occupancy_2d_cpu, ('cpu', 'both')),
-                                (eh._epic.epic_hip_set_occupancy_2d_gpu, ('gpu', 'both'))):
+        for (variant, where), wanted in zip(variants, (('cpu', 'both'), ('gpu', 'both'))):
             if process in wanted:
-                rc = variant(self, occ.ctypes.data, int(obstacle_threshold), int(no_change), flags, ct.byref(changed))
+                rc = variant(self, occ.ctypes.data, *where, *rule, ct.byref(changed))
                 if rc != 0:
                     raise RuntimeError("epic_amd: %s failed with code %d" % (variant.__name__, rc))
         return int(changed.value)
 
     def reset_free_cells(self, process='gpu'):
-        """Every unlocked interior cell back to EPIC_LOG_SPACE_FREE (the node's reset_free_cells service); ``process`` as in
-        ``set_occupancy``."""
+        """Every unlocked interior cell back to EPIC_LOG_SPACE_FREE (the node's reset_free_cells service), on a 2-D or a 3-D
+        grid; ``process`` as in ``set_occupancy``."""
         if process not in ('gpu', 'cpu', 'both'):
             raise ValueError("process must be 'gpu', 'cpu' or 'both'")
-        for variant, wanted in ((eh._epic.epic_hip_reset_free_cells_2d_cpu, ('cpu', 'both')),
-                                (eh._epic.epic_hip_reset_free_cells_2d_gpu, ('gpu', 'both'))):
+        if int(self.n) == 3:
+            variants = (eh._epic.epic_hip_reset_free_cells_3d_cpu, eh._epic.epic_hip_reset_free_cells_3d_gpu)
+        else:
+            variants = (eh._epic.epic_hip_reset_free_cells_2d_cpu, eh._epic.epic_hip_reset_free_cells_2d_gpu)
+        for variant, wanted in ((variants[0], ('cpu', 'both')),
+                                (variants[1], ('gpu', 'both'))):
             if process in wanted:
                 rc = variant(self)
                 if rc != 0:

@@ -217,6 +217,44 @@ int epic_hip_timed_occupancy_2d_gpu(EpicHarmonicT *h, const void *occ, int obsta
 int epic_hip_reset_free_cells_2d_cpu(EpicHarmonicT *h);
 int epic_hip_reset_free_cells_2d_gpu(EpicHarmonicT *h);
 
+/* ---- dense occupancy ingestion into a region, 2-D and 3-D ----------------------------------------------------------
+ * A costmap publishes rectangular updates, a depth sensor refreshes a box of voxels: these apply a block of bytes to a
+ * rectangular region of a 2-D or 3-D field (harmonic->n is 2 or 3).  A whole voxel grid is the region "the grid".
+ *   origin, extent   n entries each IN THE ORDER OF m, slowest axis first: {y0, x0} and {height, width} for n == 2 (m = {rows,
+ *                    cols}); the indices along m[0], m[1], m[2] for n == 3 (cell (x0, x1, x2) at u[(x0 * m[1] + x1) * m[2] + x2]:
+ *                    planes, rows, columns -- NOT the (x, y, z) order of the cell lists).  Both NULL: the whole grid.
+ *   occ              host pointer to extent[0] * ... * extent[n - 1] bytes, row-major in the order of m and unpitched: the
+ *                    `data` of a map_msgs/OccupancyGridUpdate as it comes, or a dense block of voxels.
+ * The region must lie inside the grid: extent[i] >= 1 and origin[i] + extent[i] <= m[i] for every i (tested without overflow);
+ * nothing is clipped.  The rule is the four-step rule of epic_hip_set_occupancy_2d_* above, with the same obstacle_threshold,
+ * no_change and flags, applied to every cell of the region that is INTERIOR to the grid: not on the border in 2-D, not on any of
+ * the six faces in 3-D.  Bytes that fall on border or face cells are ignored; cells outside the region are neither read nor
+ * written.  *changed (may be NULL) counts what it counts there, over the region.
+ * The _cpu variant edits harmonic->u and harmonic->locked.  The _gpu variant edits the device-resident state only and is an
+ * ordering point with the sequence of epic_hip_set_occupancy_2d_gpu: pending iterations are flushed, only the region's bytes
+ * cross the bus, the call synchronises, and the next two iterations run every tile -- unless EPIC_HIP_OCC_KEEP_FREE is set and
+ * *changed == 0: then the resident state is bit for bit what it was.  With both pointers NULL on a 2-D field the result is that
+ * of epic_hip_set_occupancy_2d_*.  epic_hip_timed_occupancy_region_gpu: the same call, *kernel_ms = the device time of the
+ * ingestion kernel alone (0 in multi-device mode).
+ * epic_hip_reset_free_cells_3d_*: every unlocked interior cell of a 3-D field back to EPIC_LOG_SPACE_FREE.
+ * Multi-device mode (EPIC_HIP_DEVICES): a 2-D region takes the route of epic_hip_set_occupancy_2d_gpu there (the resident cells
+ * are read back, the rule runs on the host over the window, the cells that change go through the sparse edit); results are
+ * bit-identical to one device.  For n == 3 plane-slab edits are not built: epic_hip_set_occupancy_region_gpu, the timed call and
+ * epic_hip_reset_free_cells_3d_gpu return EPIC_ERROR_INVALID_DATA with a message naming the host route,
+ * epic_hip_set_occupancy_region_cpu (epic_hip_reset_free_cells_3d_cpu) followed by harmonic_update_model_gpu.
+ * EPIC_ERROR_INVALID_DATA: a null harmonic, m, u, locked or occ; n not 2 or 3 (reset: n != 3); exactly one of origin and extent
+ * NULL; a region that does not lie inside the grid; (_gpu) no device state; (timed) a null kernel_ms.  HIP failures give the
+ * codes epic_hip_set_occupancy_2d_gpu gives for the same steps. */
+int epic_hip_set_occupancy_region_cpu(EpicHarmonicT *h, const void *occ, const unsigned int *origin, const unsigned int *extent,
+                                      int obstacle_threshold, int no_change, unsigned flags, unsigned long long *changed);
+int epic_hip_set_occupancy_region_gpu(EpicHarmonicT *h, const void *occ, const unsigned int *origin, const unsigned int *extent,
+                                      int obstacle_threshold, int no_change, unsigned flags, unsigned long long *changed);
+int epic_hip_timed_occupancy_region_gpu(EpicHarmonicT *h, const void *occ, const unsigned int *origin, const unsigned int *extent,
+                                        int obstacle_threshold, int no_change, unsigned flags, unsigned long long *changed,
+                                        float *kernel_ms);
+int epic_hip_reset_free_cells_3d_cpu(EpicHarmonicT *h);
+int epic_hip_reset_free_cells_3d_gpu(EpicHarmonicT *h);
+
 /* Diagnostic: the number of tiles the next iteration will recompute and the number of tiles (both 0 when tracking is
  * off).  Synchronises the stream and copies the list counters to the host. */
 int epic_hip_activity_stats(EpicHarmonicT *harmonic, unsigned long long *active_tiles, unsigned long long *tiles);
