@@ -31,6 +31,8 @@
 //                        the driver_* units above: it calls launchers the fake runtime does not know
 //   field3d_driver.hip   streamlines and sparse edits on a resident 3-D field (epic_hip_*_3d_gpu); kept out of the driver_* units for
 //                        the same reason
+//   field_query_driver.hip  queries of a resident field (epic_hip_sample_*_gpu, epic_hip_flow_field_gpu, epic_hip_get_*_gpu): ordering
+//                        points that write nothing; kept out of the driver_* units for the same reason
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>

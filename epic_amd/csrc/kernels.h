@@ -268,4 +268,25 @@ struct OccRegion {
 hipError_t launch_occupancy_region(float *u, uint32_t *maskw, const unsigned char *d_occ, const OccRegion &region, int pitch,
                                    int obstacle_threshold, int no_change, unsigned flags, unsigned long long *d_changed, hipStream_t stream);
 
+// ---- queries of the resident field (field_query.hip); called from field_query_driver.hip only ------------------------------
+// The field as the context holds it; a 2-D field is one plane: m0 = 1, m1 = rows.  Nothing is written to u or the masks.
+struct QueryField {
+    const float *u;
+    const uint32_t *maskw;
+    int n;                 // 2 or 3
+    int m0, m1, m2, pitch;
+};
+// One lane per point: d_points n_points x n floats (x, y[, z]); gradient: d_out n_points x n floats, else n_points floats;
+// d_status (may be null) one EPIC_HIP_QUERY_* byte per point.  The rule is field_query_rule.h.
+hipError_t launch_sample_points(const QueryField &field, unsigned n_points, const float *d_points, bool gradient, float cd, float *d_out,
+                                unsigned char *d_status, hipStream_t stream);
+// origin / extent: three entries in the order of m (2-D: {0, y0, x0} / {1, height, width}); the box must lie inside the grid (else
+// hipErrorInvalidValue).  Outputs are unpitched, row-major over the box: d_gradient n floats per cell, d_status (may be null) one byte.
+hipError_t launch_flow_field(const QueryField &field, const unsigned origin[3], const unsigned extent[3], float cd, float *d_gradient,
+                             unsigned char *d_status, hipStream_t stream);
+// values and unpacked lock bits (0 / 1) of a box (either output may be null, not both) and of k listed cells, all inside the grid
+hipError_t launch_gather_region(const QueryField &field, const unsigned origin[3], const unsigned extent[3], float *d_u, unsigned *d_locked,
+                                hipStream_t stream);
+hipError_t launch_gather_cells(const QueryField &field, unsigned k, const unsigned *d_v, float *d_u, unsigned *d_locked, hipStream_t stream);
+
 }  // namespace epic_hip

@@ -159,6 +159,15 @@ _SIGNATURES = {
                                             ct.POINTER(ct.c_float)),
     "epic_hip_reset_free_cells_3d_cpu": (_H,),
     "epic_hip_reset_free_cells_3d_gpu": (_H,),
+    # field queries: points are n floats each, cell lists n unsigned each, origin / extent n entries in the order of m
+    "epic_hip_sample_potential_cpu": (_H, ct.c_uint, ct.c_void_p, ct.c_void_p, ct.c_void_p),
+    "epic_hip_sample_potential_gpu": (_H, ct.c_uint, ct.c_void_p, ct.c_void_p, ct.c_void_p),
+    "epic_hip_sample_gradient_cpu": (_H, ct.c_uint, ct.c_void_p, ct.c_float, ct.c_void_p, ct.c_void_p),
+    "epic_hip_sample_gradient_gpu": (_H, ct.c_uint, ct.c_void_p, ct.c_float, ct.c_void_p, ct.c_void_p),
+    "epic_hip_flow_field_cpu": (_H, _UP, _UP, ct.c_float, ct.c_uint, ct.c_void_p, ct.c_void_p),
+    "epic_hip_flow_field_gpu": (_H, _UP, _UP, ct.c_float, ct.c_uint, ct.c_void_p, ct.c_void_p),
+    "epic_hip_get_cells_gpu": (_H, ct.c_uint, ct.c_void_p, ct.c_void_p, ct.c_void_p),
+    "epic_hip_get_region_gpu": (_H, _UP, _UP, ct.c_uint, ct.c_void_p, ct.c_void_p),
     "epic_hip_activity_stats": (_H, ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_ulonglong)),
     "epic_hip_activity_stats2": (_H, ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_ulonglong)),
     "epic_hip_work_done": (_H, ct.POINTER(ct.c_double), ct.c_int),
@@ -214,6 +223,12 @@ EPIC_CELL_TYPE_FREE = 2
 EPIC_HIP_OCC_KEEP_FREE = 1
 EPIC_HIP_OCC_UNSIGNED = 2
 EPIC_HIP_OCC_OVER_GOALS = 4
+# per-item statuses and the flag of the field queries (include/epic_hip.h)
+EPIC_HIP_QUERY_OK = 0
+EPIC_HIP_QUERY_INVALID_LOCATION = 1
+EPIC_HIP_QUERY_INVALID_GRADIENT = 2
+EPIC_HIP_QUERY_FLAT = 3
+EPIC_HIP_QUERY_DEVICE_OUT = 1
 
 
 def config_dump(h):

@@ -239,6 +239,144 @@ class Harmonic(eh.EpicHarmonic):
                 if rc != 0:
                     raise RuntimeError("epic_amd: %s failed with code %d" % (variant.__name__, rc))
 
+    # -- queries of the field, 2-D and 3-D -------------------------------------------------------------------
+    def _query_points(self, points):
+        n = int(self.n)
+        if n not in (2, 3):
+            raise ValueError("field queries exist for 2-D and 3-D grids, not n = %d" % n)
+        points = np.ascontiguousarray(np.asarray(points, dtype=np.float32))
+        if points.ndim != 2 or points.shape[1] != n:
+            raise ValueError("points must have shape (N, %d)" % n)
+        return n, points
+
+    def _query_region(self, origin, extent):
+        """(origin pointer, extent pointer, shape, keep-alive) of a region given in the order of m; both None: the grid"""
+        n = int(self.n)
+        if n not in (2, 3):
+            raise ValueError("field queries exist for 2-D and 3-D grids, not n = %d" % n)
+        if origin is None and extent is None:
+            return None, None, self.shape, ()
+        if origin is None or extent is None:
+            raise ValueError("origin and extent go together")
+        origin = np.ascontiguousarray(np.asarray(origin, dtype=np.uint32)).reshape(-1)
+        extent = np.ascontiguousarray(np.asarray(extent, dtype=np.uint32)).reshape(-1)
+        if origin.size != n or extent.size != n:
+            raise ValueError("origin and extent need %d entries each" % n)
+        if np.any(extent < 1) or np.any(origin.astype(np.int64) + extent > np.array(self.shape, dtype=np.int64)):
+            raise ValueError("the region must lie inside the grid")
+        UP = ct.POINTER(ct.c_uint)
+        return origin.ctypes.data_as(UP), extent.ctypes.data_as(UP), tuple(int(e) for e in extent), (origin, extent)
+
+    @staticmethod
+    def _device_out(tensor, shape, itemsize, what):
+        """data_ptr() of a torch tensor that can take a device-side result of `shape` elements of `itemsize` bytes"""
+        if tensor is None:
+            return None
+        if not tensor.is_cuda or not tensor.is_contiguous() or tuple(tensor.shape) != tuple(shape) or tensor.element_size() != itemsize:
+            raise ValueError("%s must be a contiguous device tensor of shape %s with %d-byte elements" % (what, tuple(shape), itemsize))
+        return tensor.data_ptr()
+
+    def potential_at(self, points, process='gpu'):
+        """The interpolated potential at ``points``, an (N, n) float32 array of (x, y[, z]) in cell units (x along the last
+        axis of m): epic_hip_sample_potential_gpu on the device-resident field, or _cpu on the host arrays.  Returns
+        ``(potential, status)``: N float32 and N uint8 (EPIC_HIP_QUERY_*; the potential is 0 where the status is not OK)."""
+        if process not in ('gpu', 'cpu'):
+            raise ValueError("process must be 'gpu' or 'cpu'")
+        n, points = self._query_points(points)
+        count = points.shape[0]
+        potential = np.zeros(count, dtype=np.float32)
+        status = np.zeros(count, dtype=np.uint8)
+        call = eh._epic.epic_hip_sample_potential_gpu if process == 'gpu' else eh._epic.epic_hip_sample_potential_cpu
+        rc = call(self, count, points.ctypes.data, potential.ctypes.data, status.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("epic_amd: %s failed with code %d" % (call.__name__, rc))
+        return potential, status
+
+    def gradient_at(self, points, cd_precision, process='gpu'):
+        """The normalised central-difference gradient at ``points`` (as in ``potential_at``): epic_hip_sample_gradient_*.
+        Returns ``(gradient, status)``: (N, n) float32 and N uint8; the gradient is 0 where the status is not OK."""
+        if process not in ('gpu', 'cpu'):
+            raise ValueError("process must be 'gpu' or 'cpu'")
+        n, points = self._query_points(points)
+        count = points.shape[0]
+        gradient = np.zeros((count, n), dtype=np.float32)
+        status = np.zeros(count, dtype=np.uint8)
+        call = eh._epic.epic_hip_sample_gradient_gpu if process == 'gpu' else eh._epic.epic_hip_sample_gradient_cpu
+        rc = call(self, count, points.ctypes.data, float(cd_precision), gradient.ctypes.data, status.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("epic_amd: %s failed with code %d" % (call.__name__, rc))
+        return gradient, status
+
+    def flow_field(self, cd_precision=0.5, origin=None, extent=None, process='gpu', out=None):
+        """The gradient at every cell of a region (``origin`` / ``extent``: n entries in the order of m; both None: the grid):
+        epic_hip_flow_field_*.  Returns ``(gradient, status)`` as numpy arrays of shape ``extent + (n,)`` (float32) and
+        ``extent`` (uint8).  ``out=(gradient, status)`` -- torch tensors of those shapes on the context's device, float32 and
+        uint8; ``status`` may be None -- makes the kernel write straight into them (EPIC_HIP_QUERY_DEVICE_OUT; 'gpu' only) and
+        returns them; torch's current stream is synchronised before the call."""
+        if process not in ('gpu', 'cpu'):
+            raise ValueError("process must be 'gpu' or 'cpu'")
+        o, e, shape, keep = self._query_region(origin, extent)
+        n = int(self.n)
+        if out is not None:
+            if process != 'gpu':
+                raise ValueError("out= needs process='gpu'")
+            import torch
+
+            g_out, s_out = out if isinstance(out, (tuple, list)) else (out, None)
+            g_ptr = self._device_out(g_out, shape + (n,), 4, "out[0]")
+            s_ptr = self._device_out(s_out, shape, 1, "out[1]")
+            torch.cuda.current_stream(g_out.device).synchronize()
+            rc = eh._epic.epic_hip_flow_field_gpu(self, o, e, float(cd_precision), eh.EPIC_HIP_QUERY_DEVICE_OUT, g_ptr, s_ptr)
+            if rc != 0:
+                raise RuntimeError("epic_amd: epic_hip_flow_field_gpu failed with code %d" % rc)
+            return g_out, s_out
+        gradient = np.zeros(shape + (n,), dtype=np.float32)
+        status = np.zeros(shape, dtype=np.uint8)
+        call = eh._epic.epic_hip_flow_field_gpu if process == 'gpu' else eh._epic.epic_hip_flow_field_cpu
+        rc = call(self, o, e, float(cd_precision), 0, gradient.ctypes.data, status.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("epic_amd: %s failed with code %d" % (call.__name__, rc))
+        return gradient, status
+
+    def get_cells(self, v):
+        """Value and lock state of the cells ``v`` -- a (k, n) array of (x, y[, z]) as for ``set_cells`` -- as the device holds
+        them (epic_hip_get_cells_gpu).  Returns ``(u, locked)``: k float32 and k uint32."""
+        n = int(self.n)
+        v = np.ascontiguousarray(np.asarray(v, dtype=np.uint32))
+        if n not in (2, 3) or v.ndim != 2 or v.shape[1] != n:
+            raise ValueError("v must have shape (k, n) on a 2-D or 3-D grid")
+        u = np.zeros(v.shape[0], dtype=np.float32)
+        locked = np.zeros(v.shape[0], dtype=np.uint32)
+        rc = eh._epic.epic_hip_get_cells_gpu(self, v.shape[0], v.ctypes.data, u.ctypes.data, locked.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("epic_amd: epic_hip_get_cells_gpu failed with code %d" % rc)
+        return u, locked
+
+    def get_region(self, origin=None, extent=None, out=None):
+        """Values and lock states of a region of the device-resident field (epic_hip_get_region_gpu).  Returns ``(u, locked)``
+        as numpy arrays of shape ``extent`` (float32, uint32).  ``out=(u, locked)`` -- torch device tensors of that shape,
+        float32 and int32; either may be None -- makes the kernel write straight into them and returns them."""
+        o, e, shape, keep = self._query_region(origin, extent)
+        if out is not None:
+            import torch
+
+            u_out, l_out = out
+            u_ptr = self._device_out(u_out, shape, 4, "out[0]")
+            l_ptr = self._device_out(l_out, shape, 4, "out[1]")
+            if u_ptr is None and l_ptr is None:
+                raise ValueError("out= needs at least one tensor")
+            torch.cuda.current_stream((u_out if u_out is not None else l_out).device).synchronize()
+            rc = eh._epic.epic_hip_get_region_gpu(self, o, e, eh.EPIC_HIP_QUERY_DEVICE_OUT, u_ptr, l_ptr)
+            if rc != 0:
+                raise RuntimeError("epic_amd: epic_hip_get_region_gpu failed with code %d" % rc)
+            return u_out, l_out
+        u = np.zeros(shape, dtype=np.float32)
+        locked = np.zeros(shape, dtype=np.uint32)
+        rc = eh._epic.epic_hip_get_region_gpu(self, o, e, 0, u.ctypes.data, locked.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("epic_amd: epic_hip_get_region_gpu failed with code %d" % rc)
+        return u, locked
+
     def __str__(self):
         s = "n: %d\nm: %s\nepsilon: %g\ndelta: %g\nnumIterationsToStaggerCheck: %d\ncurrentIteration: %d\n" % (
             self.n, list(self.shape), self.epsilon, self.delta, self.numIterationsToStaggerCheck,

@@ -255,6 +255,73 @@ int epic_hip_timed_occupancy_region_gpu(EpicHarmonicT *h, const void *occ, const
 int epic_hip_reset_free_cells_3d_cpu(EpicHarmonicT *h);
 int epic_hip_reset_free_cells_3d_gpu(EpicHarmonicT *h);
 
+/* ---- Field queries: point samples, flow fields, cell read-back (2-D and 3-D) -----------------------------------------
+ * Questions a caller asks of a relaxed field, answered where the field lives: harmonic->n is 2 or 3, and every call dispatches
+ * on it.  The reference answers a request for one value by copying the whole field to the host
+ * (src/epic_navigation_node_harmonic.cpp:522-542, srvGetCell -> harmonic_get_potential_values_gpu: 268 MB at 8192^2).
+ *   points          n floats each, (x, y[, z]) in cell units, x along the LAST axis of m (the convention of the path functions);
+ *   v               cell lists, n unsigned each in the same order, as for the set_cells calls;
+ *   origin, extent  n entries each in the order of m, as for epic_hip_set_occupancy_region_*; both NULL: the whole grid.  The
+ *                   region must lie inside the grid; nothing is clipped.
+ * Per-item status, one unsigned char: */
+#define EPIC_HIP_QUERY_OK                0  /* the value(s) are those of the host function */
+#define EPIC_HIP_QUERY_INVALID_LOCATION  1  /* outside the grid, or an obstacle (locked with u < 0); outputs +0.0f */
+#define EPIC_HIP_QUERY_INVALID_GRADIENT  2  /* one of the 2 n samples at +-cdPrecision is an invalid location; outputs +0.0f */
+#define EPIC_HIP_QUERY_FLAT              3  /* the norm of the central differences is zero, NaN or infinite; outputs +0.0f */
+#define EPIC_HIP_QUERY_DEVICE_OUT  1u  /* flags: the output pointers are device memory on the context's device */
+/* The anchor is the existing host functions, bit for bit: harmonic_compute_potential_2d_cpu, harmonic_compute_gradient_2d_cpu,
+ * epic_hip_compute_potential_3d_cpu, epic_hip_compute_gradient_3d_cpu.  Reads are clamped to the nearest cell and a coordinate
+ * goes to an index through a 64-bit signed truncation whose low word is kept (NaN, +-inf and |x| >= 2^63, which have none, are
+ * outside the grid), as the device walks do; the 2-D calls therefore differ from the reference's functions only where those read
+ * outside their arrays.
+ *   sample_potential  potential[i] and OK where the host function succeeds; INVALID_LOCATION and +0.0f where it returns
+ *                     EPIC_ERROR_INVALID_LOCATION.
+ *   sample_gradient   gradient holds n floats per point.  The point's own cell is not tested (the reference does not test it).
+ *                     INVALID_GRADIENT and zeros where the host function returns that code; otherwise FLAT and zeros when the
+ *                     norm (the same bits as the host's) is not a positive finite number -- !(norm > 0) || isinf(norm): the
+ *                     reference returns success with 0 / 0 components there --; otherwise OK and the host function's bits.
+ *   flow_field        for every cell of the region in row-major m order: the sample point is the cell's own index as floats
+ *                     (where the potential function returns the cell's value).  A cell that is not usable (outside, or locked
+ *                     with u < 0) gets INVALID_LOCATION and zeros; every other cell, goals included, gets what sample_gradient
+ *                     gives at that point.  gradient: n floats per cell; status: one byte per cell.
+ *   get_cells         value and lock state (0 / 1) of k cells as the device holds them.  The list is checked on the host first:
+ *                     an entry outside the grid makes the call return EPIC_ERROR_INVALID_LOCATION with the outputs untouched.
+ *   get_region        the same for a region, unpitched; either output may be NULL, not both.
+ * status may be NULL in every call.  A call returns EPIC_SUCCESS when the batch ran, whatever the items' statuses; a count of 0 is
+ * a success that touches nothing.  EPIC_ERROR_INVALID_DATA: a null harmonic, m or required pointer ((_cpu) u, locked), n not 2 or
+ * 3, an invalid region, unknown flags, (_gpu) no device state or dimensions that are not the resident ones -- what
+ * epic_hip_compute_paths_2d_gpu returns for a context that is not initialised.
+ * The _cpu calls read harmonic->u / harmonic->locked.  The _gpu calls read the device-resident state and are ordering points like
+ * the device walk: pending iterations are flushed, the kernel reads the current buffer on the library's stream, the call
+ * synchronises before it returns and frees its temporaries on every path.  They write nothing to the field or the masks: no work
+ * list is invalidated, and a tracked relaxation continues after a query with the bits and the iteration count of one that was never
+ * queried.  All input pointers are host memory.
+ * EPIC_HIP_QUERY_DEVICE_OUT (epic_hip_flow_field_gpu and epic_hip_get_region_gpu only): the output pointers are device memory on
+ * the context's device (a torch tensor's data_ptr()); the kernels write straight into them, no temporary, no copy -- a whole-grid
+ * flow field at 8192^2 is 537 MB + 67 MB, twice the field.  The call still synchronises the library's stream before it returns;
+ * work of the caller's own streams on those buffers must have finished before the call.  EPIC_ERROR_INVALID_DATA in multi-device
+ * mode and in the _cpu call.
+ * Face cells: the device masks have every face cell of the grid locked, whatever harmonic->locked says.  Host and device agree
+ * when the faces are locked obstacles in the host arrays -- what every caller of the reference and epic_amd.synthetic produce.
+ * Multi-device mode (EPIC_HIP_DEVICES): all five _gpu calls read the owned units of every slab back (values and lock bits) and
+ * answer from that snapshot with the host twin or a slice of it: results are bit-identical to one device, at the price of a whole
+ * field over the bus per call.  Per-slab query kernels are not built. */
+int epic_hip_sample_potential_cpu(EpicHarmonicT *h, unsigned int n_points, const float *points, float *potential,
+                                  unsigned char *status);
+int epic_hip_sample_potential_gpu(EpicHarmonicT *h, unsigned int n_points, const float *points, float *potential,
+                                  unsigned char *status);
+int epic_hip_sample_gradient_cpu(EpicHarmonicT *h, unsigned int n_points, const float *points, float cdPrecision, float *gradient,
+                                 unsigned char *status);
+int epic_hip_sample_gradient_gpu(EpicHarmonicT *h, unsigned int n_points, const float *points, float cdPrecision, float *gradient,
+                                 unsigned char *status);
+int epic_hip_flow_field_cpu(EpicHarmonicT *h, const unsigned int *origin, const unsigned int *extent, float cdPrecision,
+                            unsigned flags, float *gradient, unsigned char *status);
+int epic_hip_flow_field_gpu(EpicHarmonicT *h, const unsigned int *origin, const unsigned int *extent, float cdPrecision,
+                            unsigned flags, float *gradient, unsigned char *status);
+int epic_hip_get_cells_gpu(EpicHarmonicT *h, unsigned int k, const unsigned int *v, float *u_out, unsigned int *locked_out);
+int epic_hip_get_region_gpu(EpicHarmonicT *h, const unsigned int *origin, const unsigned int *extent, unsigned flags, float *u_out,
+                            unsigned int *locked_out);
+
 /* Diagnostic: the number of tiles the next iteration will recompute and the number of tiles (both 0 when tracking is
  * off).  Synchronises the stream and copies the list counters to the host. */
 int epic_hip_activity_stats(EpicHarmonicT *harmonic, unsigned long long *active_tiles, unsigned long long *tiles);
