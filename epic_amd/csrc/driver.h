@@ -42,6 +42,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <functional>
 #include <map>
@@ -250,6 +251,9 @@ struct Ctx {
     // renumbered iteration -- discards it: the state the check refers to was never touched.
     struct Ahead { bool live = false; unsigned first = 0, count = 0; } ahead;
     unsigned tick_plain = 0;       // plain updates counted since the latest harmonic_update_and_check_gpu
+    // small 3-D grids (kernels_brick3d.hip): the latest brick plan and what it was made for (driver_plan.hip: brick_plan)
+    struct BrickCache { bool valid = false; std::tuple<int, int, int, int, int, int, int, int> key; epic_hip::BrickPlan plan; };
+    mutable BrickCache brick_cache;
     bool multi() const { return !slabs.empty(); }
     size_t u_bytes() const { return (size_t)rows * pitch * sizeof(float); }
     // 2-D: the lane masks are kept twice in one block -- the standard layout, and behind it the same bits cut for the fused
@@ -298,6 +302,8 @@ int jacobi_fused_rows_per_task(const Ctx *c);
 void tune_fused_rows(Ctx *c, int kind, unsigned iteration);
 epic_hip::TilePlan tile_plan(const Ctx *c);
 bool tile_checks(const Ctx *c, const epic_hip::TilePlan &tp);
+long long brick_up_to_cells(const Ctx *c);     // LDS bricks (3-D) up to this many cells
+epic_hip::BrickPlan brick_plan(const Ctx *c);
 bool rb_pairs_tracked(const Ctx *c);
 bool rb_pairs_tracked_multi(const Ctx *c);      // the same on the slabs of the multi-device mode (2-D, at least two ghost rows)
 int rb_pairs_rows_per_task(const Ctx *c);

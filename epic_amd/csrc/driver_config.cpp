@@ -96,6 +96,17 @@ Config Config::from_env()
     e = senv("EPIC_HIP_TILE_HALO");
     if (e && atoi(e) > 0) c.tile_halo = atoi(e);
     c.tile_pipeline = !sis_zero("EPIC_HIP_TILE_PIPELINE");
+    e = senv("EPIC_HIP_BRICK");
+    if (e && (e[0] == '0' || e[0] == '1')) c.brick = e[0] - '0';
+    e = senv("EPIC_HIP_BRICK_MAX_CELLS");
+    if (e && atoll(e) >= 0) c.brick_max_cells = atoll(e);
+    e = senv("EPIC_HIP_BRICK_HALO");
+    if (e && atoi(e) > 0) c.brick_halo = atoi(e);
+    e = senv("EPIC_HIP_BRICK_DIMS");
+    if (e) {
+        int s0 = 0, s1 = 0;
+        if (sscanf(e, "%dx%d", &s0, &s1) == 2 && s0 > 0 && s1 > 0) { c.brick_s0 = s0; c.brick_s1 = s1; }
+    }
     c.defer = !is_zero("EPIC_HIP_DEFER");
     c.track_pairs = !sis_zero("EPIC_HIP_TRACK_PAIRS");
     e = senv("EPIC_HIP_TRACK_PAIR_ROWS");
@@ -140,13 +151,16 @@ std::string Config::json() const
              "\"threads\": %s, \"spin_us\": %d, \"no_fuse\": %s, \"no_graph\": %s, \"fuse_min_cells\": %lld, \"fused_rows\": %d, \"tune\": %s, "
              "\"tile\": %s, \"tile_max_cells\": %lld, \"tile_rows\": %d, \"tile_width\": %d, \"tile_halo\": %d, \"tile_pipeline\": %s, \"defer\": %s, "
              "\"track_pairs\": %s, \"track_pair_rows\": %d, \"track_switch\": %g, \"tol_finish\": %d, \"tol_finish_factor\": %g, "
-             "\"flags\": %d, \"list_waves\": %zu, \"pair3d\": %s, \"pair3d_rows\": %d, \"march_x0\": %s}",
+             "\"flags\": %d, \"list_waves\": %zu, \"pair3d\": %s, \"pair3d_rows\": %d, \"march_x0\": %s, ",
              halo, no_peer ? "true" : "false",
              threads ? "true" : "false", spin_us, no_fuse ? "true" : "false", no_graph ? "true" : "false", fuse_min_cells, fused_rows,
              tune ? "true" : "false", tile ? "true" : "false", tile_max_cells, tile_rows, tile_width, tile_halo, tile_pipeline ? "true" : "false",
              defer ? "true" : "false",
              track_pairs ? "true" : "false", track_pair_rows, track_switch, tol_finish, (double)tol_finish_factor, launch.flags, launch.list_waves,
              launch.pair3d ? "true" : "false", launch.pair3d_rows, launch.march_x0 ? "true" : "false");
+    out += t;
+    snprintf(t, sizeof t, "\"brick\": %d, \"brick_max_cells\": %lld, \"brick_halo\": %d, \"brick_dims\": [%d, %d]}", brick, brick_max_cells, brick_halo,
+             brick_s0, brick_s1);
     out += t;
     return out;
 }

@@ -56,6 +56,10 @@ struct Config {
     long long tile_max_cells = -1;   // EPIC_HIP_TILE_MAX_CELLS (-1: by arithmetic and scheme, driver_plan.hip: tile_up_to_cells)
     int tile_rows = 0, tile_width = 0, tile_halo = 0;   // EPIC_HIP_TILE_ROWS / _WIDTH / _HALO (0: the cost model)
     bool tile_pipeline = true;       // EPIC_HIP_TILE_PIPELINE=0
+    int brick = -1;                  // EPIC_HIP_BRICK=0|1: the LDS bricks of small 3-D grids off / on for every grid they can hold (-1: by arithmetic, scheme and size, driver_plan.hip: brick_up_to_cells)
+    long long brick_max_cells = -1;  // EPIC_HIP_BRICK_MAX_CELLS (-1: brick_up_to_cells)
+    int brick_halo = 0;              // EPIC_HIP_BRICK_HALO (0: the cost model)
+    int brick_s0 = 0, brick_s1 = 0;  // EPIC_HIP_BRICK_DIMS=S0xS1: planes x rows of a brick, shells included (0: the cost model)
     bool defer = true;               // EPIC_HIP_DEFER=0: harmonic_update_gpu launches one single iteration per call (as before round 6) instead of counting
     bool track_pairs = true;         // EPIC_HIP_TRACK_PAIRS=0
     int track_pair_rows = 0;         // EPIC_HIP_TRACK_PAIR_ROWS (0: 16, then 4 in the tail)

@@ -138,6 +138,20 @@ hipError_t enqueue_plain_run(Ctx *c, unsigned count, unsigned first, bool check_
         if (check_last) c->tile_delta_n = tp.tiles_r * tp.tiles_c;   // read_tile_delta reads exactly what this launch wrote
         return hipSuccess;
     }
+    const epic_hip::BrickPlan bp = brick_plan(c);
+    if (bp.halo > 0 && count >= 2) {   // small 3-D grids: LDS bricks (a single iteration is cheaper as the plain sweep: no shells to load)
+        note_iterations(c, first, count);
+        for (unsigned i = 0; i < count;) {
+            const unsigned k = std::min<unsigned>(count - i, (unsigned)bp.halo);
+            hipError_t e = epic_hip::launch_brick_3d(c->buf[c->cur], c->buf[c->cur ^ 1], c->maskw, c->m[0], c->m[1], c->pitch, bp, (int)k, c->math,
+                                                     c->redblack ? (int)((first + i) & 1u) : -1, c->stream);
+            if (e != hipSuccess) return e;
+            c->cur ^= 1;
+            c->work_full += (double)k;
+            i += k;
+        }
+        return hipSuccess;
+    }
     const bool no_fuse = c->cfg.no_fuse;
     // (the fused passes have their own 248-column tiling and no work lists: they are used when tracking is off -- or
     //  bypassed for the batch, harmonic_execute_gpu; rb_fused2d_kernel for the precise / fast arithmetic, the RB instance of
@@ -236,7 +250,11 @@ hipError_t enqueue_plain_batch(Ctx *c, unsigned count, unsigned first, bool chec
     // belong to the key: 0 = single sweeps, otherwise the task height of the pass)
     const epic_hip::TilePlan tp = tile_plan(c);
     if (tp.halo > 0 && count + (check_last ? 1u : 0u) <= (unsigned)tp.halo) return enqueue_plain_run(c, count, first, check_last);   // one launch: nothing to replay
-    const int fuse_cfg = tp.halo > 0 ? -((tp.halo * 1024 + tp.tile_rows) * 4 + tp.tile_cols / 64) : fuses_tol(c) ? jacobi_fused_rows_per_task(c) : 0;
+    const epic_hip::BrickPlan bp = brick_plan(c);   // (3-D; a context has tiles or bricks, never both)
+    if (bp.halo > 0 && count <= (unsigned)bp.halo) return enqueue_plain_run(c, count, first, check_last);   // one launch: nothing to replay
+    const int fuse_cfg = tp.halo > 0   ? -((tp.halo * 1024 + tp.tile_rows) * 4 + tp.tile_cols / 64)
+                         : bp.halo > 0 ? -((bp.halo * 1024 + bp.s0) * 1024 + bp.s1)
+                         : fuses_tol(c) ? jacobi_fused_rows_per_task(c) : 0;
     const auto key = std::make_tuple(2u * count + (check_last ? 1u : 0u), c->cur + 2 * (c->track ? 1 + c->trk.phase : 0), (int)(first & 1u), c->math,
                                      (int)c->redblack, auto_rows_per_task(c), fuse_cfg);
     if (c->graphs_broken) return enqueue_plain_run(c, count, first, check_last);

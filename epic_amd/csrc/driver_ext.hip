@@ -130,6 +130,12 @@ int epic_hip_tile_iterations(Harmonic *harmonic)
     return c ? tile_plan(c).halo : 0;
 }
 
+int epic_hip_brick_iterations(Harmonic *harmonic)
+{
+    Ctx *c = harmonic ? find_ctx(harmonic) : nullptr;
+    return c && c->pitch > 0 ? brick_plan(c).halo : 0;
+}
+
 unsigned int epic_hip_finish_iteration(Harmonic *harmonic)
 {
     Ctx *c = harmonic ? find_ctx(harmonic) : nullptr;
@@ -554,6 +560,11 @@ int epic_hip_config_dump(Harmonic *harmonic, char *buf, size_t cap)
             tp.tile_cols, tp.tiles_r, tp.tiles_c);
         add(", \"sweep_rows_per_task\": %d, \"fused_rows_per_task\": %d, \"tracked_pair_rows\": %d", auto_rows_per_task(c),
             c->math == 4 ? jacobi_fused_rows_per_task(c) : fused_rows_per_task(c), rb_pairs_rows_per_task(c));
+    }
+    if (c->pitch > 0 && c->n == 3) {
+        const epic_hip::BrickPlan bp = brick_plan(c);
+        add(", \"brick_plan\": {\"iterations_per_launch\": %d, \"brick\": [%d, %d, 64], \"owned\": [%d, %d, %d], \"bricks\": [%d, %d, %d], "
+            "\"ghosted_axes\": [%d, %d, %d]}", bp.halo, bp.s0, bp.s1, bp.t0, bp.t1, bp.tc, bp.nb0, bp.nb1, bp.nbc, bp.ghost0, bp.ghost1, bp.ghostc);
     }
     if (c->multi()) {
         add(", \"halo\": %d, \"issuing_threads\": %s, \"spin_us\": %d, \"seams\": [", c->halo, multi_has_threads(c) ? "true" : "false", c->cfg.spin_us);

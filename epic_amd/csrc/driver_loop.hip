@@ -152,6 +152,7 @@ unsigned defer_cap(const Harmonic *h, const Ctx *c)
     else {
         const epic_hip::TilePlan tp = tile_plan(c);
         if (tp.halo > 0) cap = (unsigned)tp.halo;                        // LDS tiles: iterations per launch
+        else if (brick_plan(c).halo > 0) cap = (unsigned)brick_plan(c).halo;   // LDS bricks (3-D): likewise
         else if (fuses_jacobi(c) || fuses_rb_tol(c) || fuses_rb_precise(c)) cap = 2;   // fused pairs without lists
         else if (c->n == 2 && (long long)c->rows * c->pitch <= (1ll << 22) && !c->cfg.no_graph && !c->graphs_broken && !c->track) cap = 16;   // launch-bound single sweeps: a captured graph
     }

@@ -226,6 +226,77 @@ epic_hip::TilePlan tile_plan(const Ctx *c)
     return best;
 }
 
+// Small 3-D grids (one device, no work lists): the plain iterations between two checks run several per launch on bricks that stay in
+// LDS (kernels_brick3d.hip), as the tiles above do for 2-D maps.  Up to how many cells, by arithmetic and scheme: from
+// tools/bench_bricks_3d.py (profiles/bricks_3d.txt).  EPIC_HIP_BRICK=0 off, =1 on for every grid the graphs
+// path calls small (4 Mcell); EPIC_HIP_BRICK_MAX_CELLS overrides the limit (the tests set it huge).
+long long brick_up_to_cells(const Ctx *c)
+{
+    if (c->cfg.brick == 0) return 0;
+    if (c->cfg.brick_max_cells >= 0) return c->cfg.brick_max_cells;
+    if (c->cfg.brick == 1) return 1ll << 22;
+    // Measured (profiles/bricks_3d.txt; bricks / per-iteration path in one process, three alternating repetitions, spread <= 2.4 %):
+    //   precise red-black   3.0-7.5 x per iteration of a batch and 1.12-1.57 x on harmonic_complete_gpu up to 96^3 (0.88 Mcell); 1.07 / 1.01 x at 128^3
+    //   precise Jacobi      3.9-13 x and 1.20-2.04 x up to 96^3; 1.31 / 1.04 x at 128^3 (2.1 Mcell), the largest grid that has a plan
+    //   tol, either scheme  2.3-2.7 x and 1.11-1.20 x on 32^3 ... 64^3 (x2 fits one brick column).  With x2 > 64 red-black still wins
+    //                       (1.07-1.18 x on complete) but Jacobi loses a batch at 64 x 64 x 200 (0.81 x) and has no plan from 96^3: off
+    //   fast                not measured: off
+    if (c->math == 4) return c->m[2] <= 64 ? (1ll << 18) : 0;
+    if (c->math != 0) return 0;
+    return c->redblack ? (1ll << 20) : (1ll << 21);
+}
+// halo == 0: not for this context.  Knobs: EPIC_HIP_BRICK_HALO = ghost shells = iterations per launch, EPIC_HIP_BRICK_DIMS = S0xS1,
+// planes x rows of a brick with its shells (default for both: the cost model below).  The plan is a search over a few thousand
+// candidates, and defer_cap asks for it on every counted update: it is kept with the context, keyed by everything it depends on.
+epic_hip::BrickPlan brick_plan(const Ctx *c)
+{
+    const epic_hip::BrickPlan none = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (c->n != 3 || c->multi() || c->track || c->math == 2) return none;
+#if !defined(__HIPCC__)
+    if (&epic_hip::launch_brick_3d == nullptr) return none;   // the host driver built without the kernel files (kernels.h)
+#endif
+    if ((long long)c->m[0] * c->m[1] * c->m[2] > brick_up_to_cells(c)) return none;
+    const auto key = std::make_tuple(c->m[0], c->m[1], c->m[2], c->math, (int)c->redblack, c->cfg.brick_halo, c->cfg.brick_s0, c->cfg.brick_s1);
+    if (c->brick_cache.valid && c->brick_cache.key == key) return c->brick_cache.plan;
+    const int max_rows = epic_hip::brick_3d_max_rows(c->math, c->redblack);
+    const int only_halo = c->cfg.brick_halo;
+    // The cost of an iteration, in the form of the 2-D tile's model (tile_plan above): (launch + load and store of the brick) / H + the
+    // step, which is the larger of a latency chain and the issue of the passes of one SIMD; x 1.6 per further round as soon as a CU
+    // takes a second brick.  Constants: the launch (2.7) and the round penalty (1.6) are the 2-D tile's, measured there.  The others --
+    // 0.004 per brick row for load and store, 1.0 + 0.07 per pass for the latency chain, 0.22 / 0.4 per pass for the issue -- are
+    // PLACEHOLDERS, UNFITTED ESTIMATES: scaled from the tile's by the six neighbours and six exponentials of a 3-D cell, and kept because
+    // the plans they choose are within 7 % of the best shell depth probed (profiles/bricks_3d.txt).
+    epic_hip::BrickPlan best = none;
+    double best_cost = 0.0;
+    auto consider = [&](const epic_hip::BrickPlan &p) {
+        if (p.halo == 0) return;
+        const double units = (c->redblack ? p.s1 / 2 : p.s1) * (double)p.s0, per_simd = std::ceil(units / 16.0) * 4.0;
+        const double rounds = std::ceil((double)p.nb0 * p.nb1 * p.nbc / 256.0);   // whole rounds: a brick's LDS leaves a CU room for one workgroup
+        const double step = std::max(1.0 + 0.07 * per_simd, 0.2 + (c->math == 4 ? 0.22 : 0.4) * per_simd);
+        const double cost = (rounds > 1.0 ? 1.6 * rounds / 2.0 + 0.2 : 1.0) * ((2.7 + 0.004 * p.s0 * p.s1) / p.halo + step);
+        if (best.halo == 0 || cost < best_cost) { best = p; best_cost = cost; }
+    };
+    for (int halo : {2, 3, 4, 6, 8}) {
+        const int h = only_halo ? only_halo : halo;
+        if (c->cfg.brick_s0 > 0) {
+            consider(epic_hip::brick_3d_plan(c->m[0], c->m[1], c->m[2], h, c->cfg.brick_s0, c->cfg.brick_s1, max_rows));
+        } else {
+            for (int nb0 = 1; nb0 <= 64; ++nb0)
+                for (int nb1 = 1; nb1 <= 16; ++nb1) {
+                    const int s0 = nb0 == 1 ? c->m[0] : (c->m[0] + nb0 - 1) / nb0 + 2 * h;
+                    const int s1 = nb1 == 1 ? c->m[1] : (((c->m[1] + nb1 - 1) / nb1 + 2 * h + 1) & ~1);
+                    if ((nb0 > 1 && s0 >= c->m[0]) || (nb1 > 1 && s1 >= c->m[1])) continue;   // (the shells would make it the whole axis again)
+                    consider(epic_hip::brick_3d_plan(c->m[0], c->m[1], c->m[2], h, s0, s1, max_rows));
+                }
+        }
+        if (only_halo) break;
+    }
+    c->brick_cache.valid = true;
+    c->brick_cache.key = key;
+    c->brick_cache.plan = best;
+    return best;
+}
+
 // Whether a check iteration may run as the LAST step of a tile launch (its max |du| per tile into Ctx::h_tile_delta).
 bool tile_checks(const Ctx *c, const epic_hip::TilePlan &tp)
 {
@@ -326,6 +397,7 @@ const char *plain_batch_path(const Ctx *c)
     if (fuses_rb_tol(c)) return "fused tol red-black pairs (rb_tol_fused2d_kernel)";
     if (fuses_rb_precise(c)) return "fused red-black pairs (rb_fused2d_kernel)";
     if (c->track) return c->n == 3 ? "list-driven single 3-D sweeps" : "list-driven single sweeps";
+    if (brick_plan(c).halo > 0) return "LDS bricks, several 3-D iterations per launch (brick3d_kernel)";
     if (c->n == 3) return c->math == 4 && c->cfg.launch.pair3d ? "single 3-D sweeps, two planes per wave (sweep3d_pair_kernel)" : "single 3-D sweeps (sweep3d_kernel)";
     const bool graphs = (long long)c->rows * c->pitch <= (1ll << 22) && !c->cfg.no_graph && !c->graphs_broken;
     return graphs ? "single sweeps replayed from a captured hipGraph" : "single sweeps";

@@ -239,6 +239,69 @@ hipError_t launch_pack_mask_3d(const uint32_t *locked, int m0, int m1, int m2, i
                                hipStream_t stream);
 inline size_t mask_words_3d(int m0, int m1, int pitch) { return (size_t)m0 * (size_t)m1 * (size_t)(pitch / 32); }
 
+// ---- small 3-D grids: several iterations per launch on LDS bricks (kernels_brick3d.hip) ------------------------------------
+// A brick is s0 planes x s1 rows of 64 cells along x2 in LDS.  Per axis: either the whole extent fits the brick -- then the brick
+// starts at the face, covers the axis and carries no ghost shells there (ghost = 0, one brick) -- or every brick owns t cells and
+// carries `halo` shells on both sides (s = t + 2 halo; s1 rounded up to even: red-black walks row pairs).  A launch performs up
+// to `halo` iterations.
+struct BrickPlan { int halo, s0, s1, t0, t1, tc, nb0, nb1, nbc, ghost0, ghost1, ghostc, m2; };   // halo == 0: no plan
+// Rows of 64 cells the LDS arrays of an instantiation hold beside the math tables (160 KB per workgroup): u once for red-black and
+// twice for Jacobi, and for the tol math q and n beside it.
+constexpr int kBrickRowsRb = 576, kBrickRowsJacobi = 288, kBrickRowsTolRb = 176, kBrickRowsTolJacobi = 88;
+inline int brick_3d_max_rows(int math, bool redblack)
+{
+    if (math == 4) return redblack ? kBrickRowsTolRb : kBrickRowsTolJacobi;
+    return redblack ? kBrickRowsRb : kBrickRowsJacobi;
+}
+// How an m0 x m1 x m2 grid is cut into bricks of at most s0 x s1 rows (shells included) for `halo` shells.  An axis that fits is
+// covered whole; on the others the bricks are made as small as their number allows.  halo == 0: impossible (no owned cell left,
+// or more than max_rows rows).
+inline BrickPlan brick_3d_plan(int m0, int m1, int m2, int halo, int s0, int s1, int max_rows)
+{
+    const BrickPlan none = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (halo < 1 || halo > 24 || m0 < 3 || m1 < 3 || m2 < 3 || s0 < 1 || s1 < 2) return none;
+    BrickPlan p = none;
+    p.halo = halo;
+    p.m2 = m2;
+    if (s0 >= m0) { p.s0 = p.t0 = m0; p.nb0 = 1; }
+    else {
+        if (s0 - 2 * halo < 1) return none;
+        p.nb0 = (m0 + s0 - 2 * halo - 1) / (s0 - 2 * halo);
+        p.t0 = (m0 + p.nb0 - 1) / p.nb0;
+        p.s0 = p.t0 + 2 * halo;
+        p.ghost0 = 1;
+    }
+    if (s1 >= m1) { p.s1 = (m1 + 1) & ~1; p.t1 = m1; p.nb1 = 1; }
+    else {
+        const int t = (s1 & ~1) - 2 * halo;
+        if (t < 1) return none;
+        p.nb1 = (m1 + t - 1) / t;
+        p.t1 = (m1 + p.nb1 - 1) / p.nb1;
+        p.s1 = (p.t1 + 2 * halo + 1) & ~1;
+        p.ghost1 = 1;
+    }
+    if (m2 <= 64) { p.tc = 64; p.nbc = 1; }
+    else {
+        p.tc = 64 - 2 * halo;
+        p.nbc = (m2 + p.tc - 1) / p.tc;
+        p.ghostc = 1;
+    }
+    if ((long long)p.s0 * p.s1 > max_rows) return none;
+    return p;
+}
+// `steps` (<= plan.halo) iterations in -> out (in != out, also for red-black).  parity < 0: Jacobi; else red-black, parity = number
+// of the first iteration & 1.  math: precise, fast or tol.  (No max |du| output: the check of a block is a sweep of its own.)
+// Built by hipcc -- the library -- this is an ordinary reference: a library without kernels_brick3d.hip has an unresolved symbol, an error.  The host
+// driver is also built by the host compiler alone, against a stand-in runtime that provides the launchers it knows; only there the
+// reference is WEAK, its address null, and brick_plan() (driver_plan.hip) plans no bricks.
+#if defined(__HIPCC__)
+#define EPIC_BRICK_LAUNCHER_LINKAGE
+#else
+#define EPIC_BRICK_LAUNCHER_LINKAGE __attribute__((weak))
+#endif
+hipError_t launch_brick_3d(const float *in, float *out, const uint32_t *maskw, int m0, int m1, int pitch, const BrickPlan &plan, int steps,
+                           int math, int parity, hipStream_t stream) EPIC_BRICK_LAUNCHER_LINKAGE;
+
 // ---- consumers and edits of the resident 3-D field (field_3d.hip); called from field3d_driver.hip only ----------------
 // The 3-D masks are the 2-D lane masks over the m0 * m1 rows of m2 cells: word and bit of cell (x0, x1, x2) are
 // mask_word_2d(x0 * m1 + x1, x2, pitch) and mask_bit_2d(x2).

@@ -56,6 +56,19 @@ int epic_hip_iterations_per_pass(EpicHarmonicT *harmonic);
  * is not used.  EPIC_HIP_TILE=0 switches it off; EPIC_HIP_TILE_HALO / _ROWS / _WIDTH / _MAX_CELLS tune it. */
 int epic_hip_tile_iterations(EpicHarmonicT *harmonic);
 
+/* Small 3-D grids (one device, activity tracking off -- the voxel boxes of 32^3 to 128^3 cells that are replanned at 10-30 Hz): the
+ * plain iterations between two checks run SEVERAL PER LAUNCH on bricks that stay in LDS with that many ghost shells on every
+ * axis that does not fit a brick whole (epic_amd/csrc/kernels_brick3d.hip); bit-identical to single iterations, every check
+ * iteration runs singly.  Returns the iterations one such launch advances (2, 3, 4, 6 or 8, chosen per grid by a cost model of the
+ * launch; 1 to 24 when EPIC_HIP_BRICK_HALO fixes it), 0 where the path is not used.  On by default where it was measured faster
+ * (profiles/bricks_3d.txt): the precise arithmetic up to 1 Mcell (red-black) / 2 Mcell (Jacobi), the tol
+ * arithmetic up to 0.25 Mcell on grids whose last extent is at most 64; the fast arithmetic was not measured and stays off.
+ * Activity tracking bounds it as well: the library switches tracking on by itself above 4 Mi padded cells (m0 x m1 x the last extent
+ * rounded up to 256), and a tracked context takes no bricks -- a 64 x 512 x 64 box is off by default unless EPIC_HIP_TRACK=0.
+ * Study knobs: EPIC_HIP_BRICK=0 switches it off, =1 on for every grid that has a plan; EPIC_HIP_BRICK_MAX_CELLS sets the largest
+ * grid it serves; EPIC_HIP_BRICK_HALO / EPIC_HIP_BRICK_DIMS=S0xS1 fix the shell depth and the brick's planes x rows. */
+int epic_hip_brick_iterations(EpicHarmonicT *harmonic);
+
 /* Rows per task of that fused pass in the current configuration (0: no fused pass).  On grids of at least 4 Mcell on one
  * device the height is measured on the grid itself the first time a pair of plain iterations is enqueued (a few candidates,
  * three launches each, ~10 ms, once per grid and kind of pass; results do not depend on it): before that the call returns
