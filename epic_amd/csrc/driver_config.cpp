@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <memory>
 #include <mutex>
 
@@ -107,6 +108,11 @@ Config Config::from_env()
         int s0 = 0, s1 = 0;
         if (sscanf(e, "%dx%d", &s0, &s1) == 2 && s0 > 0 && s1 > 0) { c.brick_s0 = s0; c.brick_s1 = s1; }
     }
+    c.batch = !is_zero("EPIC_HIP_BATCH");
+    c.batch_fields = sint_of("EPIC_HIP_BATCH_FIELDS", 0);
+    c.batch_halo = std::max(0, sint_of("EPIC_HIP_BATCH_HALO", 0));
+    c.batch_rows = std::max(0, sint_of("EPIC_HIP_BATCH_ROWS", 0));
+    c.batch_width = sint_of("EPIC_HIP_BATCH_WIDTH", 0);
     c.defer = !is_zero("EPIC_HIP_DEFER");
     c.track_pairs = !sis_zero("EPIC_HIP_TRACK_PAIRS");
     e = senv("EPIC_HIP_TRACK_PAIR_ROWS");
@@ -159,8 +165,9 @@ std::string Config::json() const
              track_pairs ? "true" : "false", track_pair_rows, track_switch, tol_finish, (double)tol_finish_factor, launch.flags, launch.list_waves,
              launch.pair3d ? "true" : "false", launch.pair3d_rows, launch.march_x0 ? "true" : "false");
     out += t;
-    snprintf(t, sizeof t, "\"brick\": %d, \"brick_max_cells\": %lld, \"brick_halo\": %d, \"brick_dims\": [%d, %d]}", brick, brick_max_cells, brick_halo,
-             brick_s0, brick_s1);
+    snprintf(t, sizeof t, "\"brick\": %d, \"brick_max_cells\": %lld, \"brick_halo\": %d, \"brick_dims\": [%d, %d], "
+             "\"batch\": %s, \"batch_fields\": %d, \"batch_halo\": %d, \"batch_rows\": %d, \"batch_width\": %d}", brick, brick_max_cells, brick_halo,
+             brick_s0, brick_s1, batch ? "true" : "false", batch_fields, batch_halo, batch_rows, batch_width);
     out += t;
     return out;
 }

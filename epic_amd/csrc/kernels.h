@@ -182,6 +182,22 @@ inline TilePlan tile_2d_plan(int rows, int cols, int halo, int tile_rows = 0, in
 hipError_t launch_tile_2d(const float *in, float *out, const uint32_t *maskw, int rows, int pitch, const TilePlan &plan, int steps,
                           int math, int parity, unsigned *delta_bits, hipStream_t stream, float *tile_delta = nullptr);
 
+// ---- several fields of one grid shape per launch (kernels_tile2d_batch.hip); called from batch2d_driver.hip only -----------------
+// One entry of the field table a launch reads from device memory: a context's three u buffers (the two ping-pong buffers and the
+// spare one; bufs[0] == nullptr: an empty slot of the last group), its lane masks, and where a check launch stores this field's
+// max |du| per tile (tiles_r x tiles_c floats, plain stores: may be pinned host memory).
+struct BatchField {
+    float *bufs[3];
+    const uint32_t *maskw;
+    float *tile_delta;
+};
+int tile_2d_batch_max_fields(int width);   // fields one workgroup holds of the narrow (4) and the wide (2) LDS tile; 0: no such tile
+// `steps` (<= plan.halo) red-black iterations with the precise arithmetic on every field of d_fields[0 .. groups x fields_per_group),
+// from each field's bufs[src] into its bufs[dst]; parity = number of the first iteration & 1; check: the last step's maxima go to the
+// fields' tile_delta.  fields_per_group: 1, 2 or 4, at most tile_2d_batch_max_fields(plan's width).
+hipError_t launch_tile_2d_batch(const BatchField *d_fields, int groups, int fields_per_group, int src, int dst, int rows, int pitch,
+                                const TilePlan &plan, int steps, int parity, bool check, hipStream_t stream);
+
 // ---- streamlines on the resident field (path_2d.hip): one lane per start point ----------------
 // d_pts: n_paths x 2 * max_points floats; d_k: points per path (0 on failure); d_rc: EPIC_* code per path.
 hipError_t launch_follow_paths_2d(const float *u, const uint32_t *maskw, int rows, int cols, int pitch, unsigned n_paths,

@@ -169,6 +169,11 @@ _SIGNATURES = {
     "epic_hip_flow_field_gpu": (_H, _UP, _UP, ct.c_float, ct.c_uint, ct.c_void_p, ct.c_void_p),
     "epic_hip_get_cells_gpu": (_H, ct.c_uint, ct.c_void_p, ct.c_void_p, ct.c_void_p),
     "epic_hip_get_region_gpu": (_H, _UP, _UP, ct.c_uint, ct.c_void_p, ct.c_void_p),
+    # several fields per call: an array of Harmonic pointers, one return code per field (may be None)
+    "epic_hip_execute_batch_gpu": (ct.POINTER(_H), ct.c_uint, ct.c_uint, ct.POINTER(ct.c_int)),
+    "epic_hip_complete_batch_gpu": (ct.POINTER(_H), ct.c_uint, ct.c_uint, ct.POINTER(ct.c_int)),
+    "epic_hip_batch_plan": (ct.POINTER(_H), ct.c_uint, _UP, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int), ct.POINTER(ct.c_int),
+                            ct.POINTER(ct.c_int)),
     "epic_hip_activity_stats": (_H, ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_ulonglong)),
     "epic_hip_activity_stats2": (_H, ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_ulonglong)),
     "epic_hip_work_done": (_H, ct.POINTER(ct.c_double), ct.c_int),
@@ -230,6 +235,22 @@ EPIC_HIP_QUERY_INVALID_LOCATION = 1
 EPIC_HIP_QUERY_INVALID_GRADIENT = 2
 EPIC_HIP_QUERY_FLAT = 3
 EPIC_HIP_QUERY_DEVICE_OUT = 1
+
+
+def field_array(fields):
+    """The `EpicHarmonicT *const *fields` argument of the batch calls from a sequence of EpicHarmonic objects (None: a null member)."""
+    return (_H * len(fields))(*[ct.cast(ct.pointer(f), _H) if f is not None else _H() for f in fields])   # (subclasses of the struct too)
+
+
+def batch_plan(fields):
+    """epic_hip_batch_plan as a dict: how many of `fields` the batch calls would take through the batched kernel now, and its plan."""
+    batched = ct.c_uint(0)
+    plan = [ct.c_int(0) for _ in range(4)]
+    rc = _epic.epic_hip_batch_plan(field_array(fields), len(fields), ct.byref(batched), *[ct.byref(p) for p in plan])
+    if rc != 0:
+        raise RuntimeError("epic_amd: epic_hip_batch_plan failed with code %d" % rc)
+    return dict(batched=batched.value, fields_per_workgroup=plan[0].value, halo=plan[1].value, tile_rows=plan[2].value,
+                tile_cols=plan[3].value)
 
 
 def config_dump(h):

@@ -382,3 +382,31 @@ class Harmonic(eh.EpicHarmonic):
             self.n, list(self.shape), self.epsilon, self.delta, self.numIterationsToStaggerCheck,
             self.currentIteration)
         return s
+
+
+def solve_batch(fields, numThreads=1024, epsilon=None):
+    """Relax several ``Harmonic`` objects in ONE call (epic_hip_complete_batch_gpu): a field per robot, per candidate goal, per
+    hypothesis, on one map.  Every field ends exactly as its own ``solve(process='gpu')`` would leave it; the fields that share a
+    shape and a checking period and are in the library's default mode advance together on the device, the others one after
+    another inside the call.  ``epsilon``: a scalar for all, one value per field, or None to keep each field's own.  Raises
+    ``RuntimeError`` naming the first field that failed and its code.  Returns (wall-time, cpu-time) of the call, like ``solve``."""
+    fields = list(fields)
+    if epsilon is not None:
+        eps = np.broadcast_to(np.asarray(epsilon, dtype=np.float64), (len(fields),))
+        for f, e in zip(fields, eps):
+            f.epsilon = float(e)
+    codes = (ct.c_int * max(len(fields), 1))()
+    timing = (time.time(), time.process_time())
+    result = eh._epic.epic_hip_complete_batch_gpu(eh.field_array(fields), len(fields), int(numThreads), codes)
+    timing = (time.time() - timing[0], time.process_time() - timing[1])
+    if result != 0:
+        failed = [i for i in range(len(fields)) if codes[i] != 0]
+        # a field that failed keeps whatever device state its sequence had reached, as after a failed harmonic_complete_gpu: release it
+        for i in failed:
+            for release in (eh._epic.harmonic_uninitialize_dimension_size_gpu, eh._epic.harmonic_uninitialize_potential_values_gpu,
+                            eh._epic.harmonic_uninitialize_locked_gpu, eh._epic.harmonic_uninitialize_gpu):
+                release(fields[i])
+        if failed:
+            raise RuntimeError("epic_amd: field %d of the batch failed with code %d" % (failed[0], codes[failed[0]]))
+        raise RuntimeError("epic_amd: epic_hip_complete_batch_gpu failed with code %d" % result)
+    return timing

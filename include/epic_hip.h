@@ -398,6 +398,31 @@ int epic_hip_multi_report(EpicHarmonicT *harmonic, char *buf, size_t cap);
 int epic_hip_config_dump(EpicHarmonicT *harmonic, char *buf, size_t cap);
 int epic_hip_config_reload(EpicHarmonicT *harmonic);
 
+/* ---- several fields per call: a field per robot, per candidate goal, per hypothesis, all on one map ----------
+ * epic_hip_execute_batch_gpu: every fields[i] ends exactly as harmonic_execute_gpu(fields[i], numThreads) alone would leave it -- host u,
+ * currentIteration, delta and the released device state, bit for bit (with the library's defaults therefore harmonic_complete_cpu's).
+ * epic_hip_complete_batch_gpu: ... as harmonic_complete_gpu(fields[i], numThreads) would: initialise x3, execute, uninitialise x3.
+ * Fields are independent: one that converges (the reference's rule: a converged check with currentIteration >= max(m)) is read back
+ * and leaves the batch, the others go on.  results (may be NULL) receives each field's own return code; the call returns EPIC_SUCCESS
+ * or the first other code in index order.  fields == NULL, count == 0 or the same pointer twice: EPIC_ERROR_INVALID_DATA;
+ * numThreads % 32 != 0: EPIC_ERROR_INVALID_CUDA_PARAM; nothing runs then.  A field that fails harmonic_execute_gpu's own validation
+ * (a null member, epsilon <= 0, stagger 0, no device state, n = 4) gets its code in results[i]; the other fields run.  A device error
+ * inside a batched block gives every field still in the batch that code and leaves its context in the state its last check describes.
+ * WHERE the iterations run: fields with n == 2 that share m and numIterationsToStaggerCheck, whose contexts are in the library's
+ * default mode (precise math, red-black scheme, one device) on a grid the LDS tiles serve (epic_hip_tile_iterations > 0), advance
+ * TOGETHER -- one launch for all of them, a workgroup holding the same tile of up to four fields (epic_amd/csrc/kernels_tile2d_batch.hip);
+ * epsilon may differ per field.  Every other field (tol or fast math, Jacobi, 3-D, a shape of its own, fewer fields of a shape than the
+ * measured crossover: two up to 0.25 Mcell, four above) runs through harmonic_execute_gpu inside the same call.  Both calls are ordering points for every field.  EPIC_HIP_BATCH=0: every field through harmonic_execute_gpu.
+ * Study knobs: EPIC_HIP_BATCH_FIELDS (fields per workgroup: 1, 2, 4), EPIC_HIP_BATCH_HALO / _ROWS / _WIDTH (the tiles' geometry).
+ * Measured against a loop of harmonic_complete_gpu: DESIGN.md section 4.13, profiles/batch_2d.txt. */
+int epic_hip_execute_batch_gpu(EpicHarmonicT *const *fields, unsigned int count, unsigned int numThreads, int *results);
+int epic_hip_complete_batch_gpu(EpicHarmonicT *const *fields, unsigned int count, unsigned int numThreads, int *results);
+/* What the two calls above would do with these fields now: *batched = how many go through the batched kernel (0: none), and the
+ * plan of the first group of them -- fields per workgroup, ghost rings = iterations per launch, owned rows and columns of a tile
+ * (all 0 when nothing is batched).  Any output may be NULL.  The plan is made again whenever fields have left the batch. */
+int epic_hip_batch_plan(EpicHarmonicT *const *fields, unsigned int count, unsigned int *batched, int *fields_per_workgroup, int *halo,
+                        int *tile_rows, int *tile_cols);
+
 /* Geometry of the device-resident state: pitch in floats, bytes of one u buffer, bytes of the packed mask. */
 int epic_hip_get_layout(EpicHarmonicT *harmonic, unsigned int *pitch, size_t *u_bytes, size_t *mask_bytes);
 
