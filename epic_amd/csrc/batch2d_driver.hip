@@ -1,15 +1,16 @@
-// batch2d_driver.hip -- host driver of the batched 2-D relaxation (include/epic_hip.h: epic_hip_execute_batch_gpu,
-// epic_hip_complete_batch_gpu, epic_hip_batch_plan): SEVERAL fields of one grid shape per launch on shared LDS tiles
-// (kernels_tile2d_batch.hip).  Every call of that launcher lives here; like occupancy_driver.hip this is not one of the driver_*
-// units (driver.h), which are built against a fake runtime that knows only their launchers, and none of them calls into this one.
+// batch2d_driver.hip -- host driver of the batched relaxation (include/epic_hip.h: epic_hip_execute_batch_gpu,
+// epic_hip_complete_batch_gpu, epic_hip_batch_plan): SEVERAL fields of one grid shape per launch, 2-D maps on shared LDS tiles
+// (kernels_tile2d_batch.hip) and -- the file has kept its name -- 3-D voxel fields on LDS bricks (kernels_brick3d_batch.hip).  Every
+// call of those two launchers lives here; like occupancy_driver.hip this is not one of the driver_* units (driver.h), which are built
+// against a fake runtime that knows only their launchers, and none of them calls into this one.
 //
 // What a batch call does with a field is what harmonic_execute_gpu does with it alone -- the same start (pending iterations flushed,
 // currentIteration = 0, harmonic_initialize_gpu), the same iterations in the same order with the same arithmetic, the reference's exit
 // rule (a converged check with currentIteration >= max(m)), the same end (harmonic_get_potential_values_gpu, harmonic_uninitialize_gpu)
 // -- so u, currentIteration, delta and the released device state are the single call's bit for bit.  Only WHERE the iterations run
 // differs: the fields that share a shape and a checking period and are in the library's default mode (precise, red-black, a grid the
-// single-field tile path takes) advance together, one launch for all of them; every other field goes through harmonic_execute_gpu
-// inside the same call.
+// single-field tile path -- 3-D: the single-field brick path -- takes) advance together, one launch for all of them; every other
+// field goes through harmonic_execute_gpu inside the same call.
 #include "driver.h"
 
 using namespace epic_drv;
@@ -24,16 +25,20 @@ struct Member {
     unsigned m_max;   // max(m): no exit before this many iterations (harmonic_gpu.cu:266)
 };
 struct BatchPlan { epic_hip::TilePlan tp; int fields; };   // fields per workgroup; 0: no plan
+struct BrickBatchPlan { epic_hip::BrickPlan bp; int capacity; };   // 3-D: the bricks and the LDS capacity (rows) of the instantiation; 0: no plan
+constexpr long long kBrickDeltaCap = 4096;   // bricks of a launch (their maxima are read per field after every block)
 
 // A field the batched kernel can take: everything harmonic_execute_gpu validates holds, and the context is in the library's
-// default mode on a grid the single-field tile path would take with its per-tile checks.
+// default mode on a grid the single-field tile path would take with its per-tile checks -- or, 3-D, one the single-field path
+// would put on bricks (which leaves out tracked contexts and grids above brick_up_to_cells).
 bool batchable(Harmonic *h, Ctx *c)
 {
     if (!h || !h->m || !h->u || !h->locked || !(h->epsilon > 0.0f) || !h->d_m || !h->d_u || !h->d_locked || h->d_delta ||
         h->numIterationsToStaggerCheck == 0)
         return false;
-    if (!ready(h, c) || c->n != 2 || c->multi() || !c->devices.empty() || !c->cfg.batch || !c->cfg.tile_pipeline) return false;
+    if (!ready(h, c) || (c->n != 2 && c->n != 3) || c->multi() || !c->devices.empty() || !c->cfg.batch || !c->cfg.tile_pipeline) return false;
     if (c->math != 0 || !c->redblack) return false;
+    if (c->n == 3) return brick_plan(c).halo > 0;
     return tile_checks(c, tile_plan(c));
 }
 
@@ -96,6 +101,69 @@ BatchPlan batch_plan(int rows, int cols, unsigned live, const Config &cfg)
     return best;
 }
 
+// 3-D: from how many voxel fields of this shape the batched brick kernel is taken (fewer: the per-field loop; ~0u: never).  A lone field
+// is never batched.  Read from profiles/batch_3d.txt (epic_hip_complete_batch_gpu / loop of harmonic_complete_gpu in one process, three
+// alternating repetitions): the batch is taken only where a row shows it faster than the loop by more than that row's spread, and a
+// size without a row keeps the loop.
+//   16^3   loop: 1.08 x at four fields is the only row that passes; 16 and 32 fields LOSE (0.98, 0.97 x, spread <= 2.8 %)
+//   32^3   from four: 1.05 x, 1.03 x, 1.02 x, 1.03 x, 1.03 x at 4 ... 64 fields (spread <= 1.4 %); two fields 1.05 x inside a spread of 5.1 %
+//   64^3   from two: 1.02 x (spread 1.8 %), then 1.03 x;  64 x 64 x 200 (0.82 Mcell, shells along x2 too) from two: 1.04 x (1.3 %), 1.07-1.08 x
+//   96^3   from four: 1.03-1.04 x (spread <= 1.4 %); two fields 1.00 x
+// Sizes between two measured ones take the stricter neighbour; below 32^3 and above 96^3 nothing supports the batch.
+unsigned batch3d_from_fields(const int *m)
+{
+    const long long cells = (long long)m[0] * m[1] * m[2];
+    if (cells < 32 * 32 * 32 || cells > 96 * 96 * 96) return ~0u;
+    return cells >= 64 * 64 * 64 && cells <= 64 * 64 * 200 ? 2u : 4u;   // (64^3 and 64 x 64 x 200 both take two; 32^3 ... 64^3 and up to 96^3 four)
+}
+
+// Shell depth, bricks per axis and LDS capacity for `live` voxel fields of m0 x m1 x m2 cells, in brick_plan's cost form
+// (driver_plan.hip; DESIGN.md sections 4.12, 4.14): an iteration of ONE workgroup costs (launch + load and store of the brick) / H plus
+// the step -- the larger of a latency chain and the issue of one SIMD's passes --, x 1.6 per further round.  Three things differ.
+// The workgroups of a launch are bricks x live fields.  A round is 256 workgroups at capacity 576 and 512 at capacity 288, where a CU
+// holds two -- and as soon as a CU does hold two they share its issue, so the issue term counts twice there while the latency chain
+// of one hides behind the other: that is the whole case for the small capacity, and an ASSUMPTION of this model, not a fit.  And with
+// many fields a field no longer has to fill the chip: larger bricks with less shell recomputation come into reach, as the wide tile
+// did in 2-D.  The per-pass constants (0.004 per brick row, 1.0 + 0.07 per pass, 0.4 per pass) are brick_plan's PLACEHOLDERS,
+// UNFITTED ESTIMATES, reused as they are.  The bits do not depend on any of it.  Study knobs: EPIC_HIP_BATCH_HALO (shell depth),
+// EPIC_HIP_BRICK_DIMS (S0xS1), EPIC_HIP_BATCH_BRICK_ROWS (capacity).
+BrickBatchPlan batch_brick_plan(const int *m, unsigned live, const Config &cfg)
+{
+    BrickBatchPlan best = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, 0};
+    double best_cost = 0.0;
+    for (int capacity : {epic_hip::kBrickBatchRows, epic_hip::kBrickBatchRowsHalf}) {
+        if (cfg.batch_brick_rows && capacity != cfg.batch_brick_rows) continue;
+        const bool half = capacity == epic_hip::kBrickBatchRowsHalf;
+        auto consider = [&](const epic_hip::BrickPlan &p) {
+            const long long bricks = (long long)p.nb0 * p.nb1 * p.nbc;
+            if (p.halo == 0 || bricks > kBrickDeltaCap) return;
+            const double wgs = (double)bricks * live;
+            const double per_simd = std::ceil((p.s1 / 2) * (double)p.s0 / 16.0) * 4.0;
+            const double rounds = std::ceil(wgs / (half ? 512.0 : 256.0));
+            const double issue = (half && wgs > 256.0 ? 2.0 : 1.0) * 0.4 * per_simd;
+            const double step = std::max(1.0 + 0.07 * per_simd, 0.2 + issue);
+            const double cost = (rounds > 1.0 ? 1.6 * rounds / 2.0 + 0.2 : 1.0) * ((2.7 + 0.004 * p.s0 * p.s1) / p.halo + step);
+            if (best.capacity == 0 || cost < best_cost) { best = BrickBatchPlan{p, capacity}; best_cost = cost; }
+        };
+        for (int halo : {2, 3, 4, 6, 8}) {
+            const int h = cfg.batch_halo ? cfg.batch_halo : halo;
+            if (cfg.brick_s0 > 0) {
+                consider(epic_hip::brick_3d_plan(m[0], m[1], m[2], h, cfg.brick_s0, cfg.brick_s1, capacity));
+            } else {
+                for (int nb0 = 1; nb0 <= 64; ++nb0)
+                    for (int nb1 = 1; nb1 <= 16; ++nb1) {
+                        const int s0 = nb0 == 1 ? m[0] : (m[0] + nb0 - 1) / nb0 + 2 * h;
+                        const int s1 = nb1 == 1 ? m[1] : (((m[1] + nb1 - 1) / nb1 + 2 * h + 1) & ~1);
+                        if ((nb0 > 1 && s0 >= m[0]) || (nb1 > 1 && s1 >= m[1])) continue;   // (the shells would make it the whole axis again)
+                        consider(epic_hip::brick_3d_plan(m[0], m[1], m[2], h, s0, s1, capacity));
+                    }
+            }
+            if (cfg.batch_halo) break;
+        }
+    }
+    return best;
+}
+
 // What a batch call does with the fields as they are now: rc[i] = -1 for a field that goes through harmonic_execute_gpu; the
 // others in groups of one shape and one checking period, each at least batch_from_fields() strong, in the order of their first member.
 std::vector<std::vector<Member>> group_fields(EpicHarmonicT *const *fields, unsigned count)
@@ -105,9 +173,10 @@ std::vector<std::vector<Member>> group_fields(EpicHarmonicT *const *fields, unsi
         Harmonic *h = fields[i];
         Ctx *c = h ? find_ctx(h) : nullptr;
         if (!batchable(h, c)) continue;
-        const Member m = {h, c, i, std::max(h->m[0], h->m[1])};
-        auto same = [&](const std::vector<Member> &g) {
-            return g[0].c->rows == c->rows && g[0].c->cols == c->cols && g[0].h->numIterationsToStaggerCheck == h->numIterationsToStaggerCheck;
+        const Member m = {h, c, i, std::max(std::max(h->m[0], h->m[1]), c->n == 3 ? h->m[2] : 0u)};
+        auto same = [&](const std::vector<Member> &g) {   // (3-D: rows = m[0] m[1], so all three extents are compared)
+            return g[0].c->n == c->n && g[0].c->m[0] == c->m[0] && g[0].c->rows == c->rows && g[0].c->cols == c->cols &&
+                   g[0].h->numIterationsToStaggerCheck == h->numIterationsToStaggerCheck;
         };
         auto it = std::find_if(groups.begin(), groups.end(), same);
         if (it == groups.end()) groups.push_back({m});
@@ -117,6 +186,9 @@ std::vector<std::vector<Member>> group_fields(EpicHarmonicT *const *fields, unsi
                                 [](const std::vector<Member> &g) {
                                     // (a forced EPIC_HIP_BATCH_FIELDS batches from two fields: how the crossover is measured)
                                     const Ctx *c = g[0].c;
+                                    if (c->n == 3)   // (a forced F, capacity or shell depth batches from two fields: how the crossover is measured)
+                                        return g.size() < (c->cfg.batch_fields || c->cfg.batch_brick_rows || c->cfg.batch_halo ? 2u : batch3d_from_fields(c->m)) ||
+                                               batch_brick_plan(c->m, (unsigned)g.size(), c->cfg).capacity == 0;
                                     return g.size() < (c->cfg.batch_fields ? 2u : batch_from_fields((long long)c->rows * c->cols)) ||
                                            batch_plan(g[0].c->rows, g[0].c->cols, (unsigned)g.size(), g[0].c->cfg).fields == 0;
                                 }),
@@ -161,12 +233,15 @@ struct Shared {
 // never writes the buffer it started from, so whatever fails in it leaves every context in the state its last read check describes.
 // After a block the per-field maxima are read, converged fields are read back and leave, the table is repacked so that the workgroups
 // stay full, and the plan is made again for the fields that are left.  (The next block is NOT enqueued ahead of the check's read, as
-// the single-field loop does: DESIGN.md section 4.13.)
+// the single-field loop does: DESIGN.md section 4.13.)  A group of 3-D fields runs the same loop on bricks: only the plan and the
+// launch differ (the third buffer of tiles_pipeline_ready is rows x pitch floats, and a 3-D context's rows are m[0] m[1]).
 void run_group(std::vector<Member> &members, unsigned numThreads, int *rc, const char *fn)
 {
     const Config cfg = members[0].c->cfg;
     const int rows = members[0].c->rows, cols = members[0].c->cols, pitch = members[0].c->pitch;
     const unsigned stagger = members[0].h->numIterationsToStaggerCheck;
+    const bool voxels = members[0].c->n == 3;
+    const int m3[3] = {members[0].c->m[0], members[0].c->m[1], members[0].c->m[2]};
     std::vector<Member> live;
     for (const Member &m : members) {
         // an ordering point for every field, and the start of its relaxation (harmonic_execute_gpu)
@@ -201,9 +276,18 @@ void run_group(std::vector<Member> &members, unsigned numThreads, int *rc, const
     Shared sh;
     if (!sh.make(live.size() + 3)) return fail_all(EPIC_ERROR_DEVICE_MALLOC, "Failed to allocate the field table of the batch.");
 
+    BatchPlan plan = {{0, 0, 0, 0, 0}, 0};
+    BrickBatchPlan bplan = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, 0};
+    size_t planned_for = 0;
     while (!live.empty()) {
-        const BatchPlan plan = batch_plan(rows, cols, (unsigned)live.size(), cfg);
-        const int F = plan.fields, tiles = plan.tp.tiles_r * plan.tp.tiles_c;
+        if (planned_for != live.size()) {   // (again whenever fields have retired)
+            if (voxels) bplan = batch_brick_plan(m3, (unsigned)live.size(), cfg);
+            else plan = batch_plan(rows, cols, (unsigned)live.size(), cfg);
+            planned_for = live.size();
+        }
+        const int F = voxels ? (bplan.capacity ? 1 : 0) : plan.fields;
+        const int tiles = voxels ? bplan.bp.nb0 * bplan.bp.nb1 * bplan.bp.nbc : plan.tp.tiles_r * plan.tp.tiles_c;
+        const int halo = voxels ? bplan.bp.halo : plan.tp.halo;
         if (F == 0) return fail_all(EPIC_ERROR_KERNEL_EXECUTION, "No tile plan for the batch.");
         const int groups = ((int)live.size() + F - 1) / F;
         if (!sh.hold_deltas(live.size() * (size_t)tiles)) return fail_all(EPIC_ERROR_DEVICE_MALLOC, "Failed to allocate pinned memory for the batch's checks.");
@@ -221,10 +305,14 @@ void run_group(std::vector<Member> &members, unsigned numThreads, int *rc, const
         const unsigned total = first % stagger == 0 ? 1u : stagger - first % stagger + 1u;
         int src = 0;
         for (unsigned i = 0; i < total;) {
-            const unsigned k = std::min<unsigned>(total - i, (unsigned)plan.tp.halo);
+            const unsigned k = std::min<unsigned>(total - i, (unsigned)halo);
             const int dst = src == 1 ? 2 : 1;
-            if (epic_hip::launch_tile_2d_batch(sh.d_table, groups, F, src, dst, rows, pitch, plan.tp, (int)k, (int)((first + i) & 1u), i + k == total,
-                                               sh.stream) != hipSuccess) {
+            const int parity = (int)((first + i) & 1u);
+            const hipError_t e = voxels ? epic_hip::launch_brick_3d_batch(sh.d_table, groups, src, dst, m3[0], m3[1], pitch, bplan.bp, bplan.capacity, (int)k,
+                                                                          parity, i + k == total, sh.stream)
+                                        : epic_hip::launch_tile_2d_batch(sh.d_table, groups, F, src, dst, rows, pitch, plan.tp, (int)k, parity, i + k == total,
+                                                                         sh.stream);
+            if (e != hipSuccess) {
                 (void)hipStreamSynchronize(sh.stream);
                 return fail_all(EPIC_ERROR_KERNEL_EXECUTION, "Failed to execute the batched 'Jacobi update' kernel.");
             }
@@ -360,7 +448,12 @@ int epic_hip_batch_plan(EpicHarmonicT *const *fields, unsigned int count, unsign
     unsigned n = 0;
     for (const auto &g : groups) n += (unsigned)g.size();
     BatchPlan plan = {{0, 0, 0, 0, 0}, 0};
-    if (!groups.empty()) plan = batch_plan(groups[0][0].c->rows, groups[0][0].c->cols, (unsigned)groups[0].size(), groups[0][0].c->cfg);
+    if (!groups.empty() && groups[0][0].c->n == 3) {   // a 3-D group: one field per workgroup, shells, and the brick's planes and rows
+        const BrickBatchPlan b = batch_brick_plan(groups[0][0].c->m, (unsigned)groups[0].size(), groups[0][0].c->cfg);
+        plan = BatchPlan{{b.bp.halo, b.bp.s0, b.bp.s1, 0, 0}, b.capacity ? 1 : 0};
+    } else if (!groups.empty()) {
+        plan = batch_plan(groups[0][0].c->rows, groups[0][0].c->cols, (unsigned)groups[0].size(), groups[0][0].c->cfg);
+    }
     if (batched) *batched = n;
     if (fields_per_workgroup) *fields_per_workgroup = plan.fields;
     if (halo) *halo = plan.tp.halo;

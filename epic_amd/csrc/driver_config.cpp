@@ -113,6 +113,8 @@ Config Config::from_env()
     c.batch_halo = std::max(0, sint_of("EPIC_HIP_BATCH_HALO", 0));
     c.batch_rows = std::max(0, sint_of("EPIC_HIP_BATCH_ROWS", 0));
     c.batch_width = sint_of("EPIC_HIP_BATCH_WIDTH", 0);
+    c.batch_brick_rows = sint_of("EPIC_HIP_BATCH_BRICK_ROWS", 0);
+    if (c.batch_brick_rows != 288 && c.batch_brick_rows != 576) c.batch_brick_rows = 0;
     c.defer = !is_zero("EPIC_HIP_DEFER");
     c.track_pairs = !sis_zero("EPIC_HIP_TRACK_PAIRS");
     e = senv("EPIC_HIP_TRACK_PAIR_ROWS");
@@ -166,8 +168,8 @@ std::string Config::json() const
              launch.pair3d ? "true" : "false", launch.pair3d_rows, launch.march_x0 ? "true" : "false");
     out += t;
     snprintf(t, sizeof t, "\"brick\": %d, \"brick_max_cells\": %lld, \"brick_halo\": %d, \"brick_dims\": [%d, %d], "
-             "\"batch\": %s, \"batch_fields\": %d, \"batch_halo\": %d, \"batch_rows\": %d, \"batch_width\": %d}", brick, brick_max_cells, brick_halo,
-             brick_s0, brick_s1, batch ? "true" : "false", batch_fields, batch_halo, batch_rows, batch_width);
+             "\"batch\": %s, \"batch_fields\": %d, \"batch_halo\": %d, \"batch_rows\": %d, \"batch_width\": %d, \"batch_brick_rows\": %d}", brick, brick_max_cells, brick_halo,
+             brick_s0, brick_s1, batch ? "true" : "false", batch_fields, batch_halo, batch_rows, batch_width, batch_brick_rows);
     out += t;
     return out;
 }

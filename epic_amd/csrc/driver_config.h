@@ -63,6 +63,7 @@ struct Config {
     bool batch = true;               // EPIC_HIP_BATCH=0: epic_hip_execute_batch_gpu / _complete_batch_gpu run every field through harmonic_execute_gpu (batch2d_driver.hip)
     int batch_fields = 0;            // EPIC_HIP_BATCH_FIELDS: fields per workgroup of the batched tile kernel, 1 | 2 | 4 (0: the cost model)
     int batch_halo = 0, batch_rows = 0, batch_width = 0;   // EPIC_HIP_BATCH_HALO / _ROWS / _WIDTH: its geometry, as the EPIC_HIP_TILE_* knobs (0: the cost model)
+    int batch_brick_rows = 0;        // EPIC_HIP_BATCH_BRICK_ROWS=288|576: LDS capacity of the batched 3-D bricks (0: the cost model); their shell depth is EPIC_HIP_BATCH_HALO, their shape EPIC_HIP_BRICK_DIMS
     bool defer = true;               // EPIC_HIP_DEFER=0: harmonic_update_gpu launches one single iteration per call (as before round 6) instead of counting
     bool track_pairs = true;         // EPIC_HIP_TRACK_PAIRS=0
     int track_pair_rows = 0;         // EPIC_HIP_TRACK_PAIR_ROWS (0: 16, then 4 in the tail)

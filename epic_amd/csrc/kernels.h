@@ -185,7 +185,8 @@ hipError_t launch_tile_2d(const float *in, float *out, const uint32_t *maskw, in
 // ---- several fields of one grid shape per launch (kernels_tile2d_batch.hip); called from batch2d_driver.hip only -----------------
 // One entry of the field table a launch reads from device memory: a context's three u buffers (the two ping-pong buffers and the
 // spare one; bufs[0] == nullptr: an empty slot of the last group), its lane masks, and where a check launch stores this field's
-// max |du| per tile (tiles_r x tiles_c floats, plain stores: may be pinned host memory).
+// max |du| per tile (tiles_r x tiles_c floats, plain stores: may be pinned host memory).  The 3-D batch (kernels_brick3d_batch.hip)
+// uses the same entry: its "tiles" are the bricks of the launch.
 struct BatchField {
     float *bufs[3];
     const uint32_t *maskw;
@@ -317,6 +318,18 @@ inline BrickPlan brick_3d_plan(int m0, int m1, int m2, int halo, int s0, int s1,
 #endif
 hipError_t launch_brick_3d(const float *in, float *out, const uint32_t *maskw, int m0, int m1, int pitch, const BrickPlan &plan, int steps,
                            int math, int parity, hipStream_t stream) EPIC_BRICK_LAUNCHER_LINKAGE;
+
+// ---- several 3-D fields of one grid shape per launch (kernels_brick3d_batch.hip); called from batch2d_driver.hip only -------------
+// The LDS capacities brick3d_batch_kernel is built for, in rows of 64 cells: the single-field red-black brick (one workgroup per
+// CU) and half of it (two workgroups per CU).  plan: brick_3d_plan() with one of them as max_rows.
+constexpr int kBrickBatchRows = kBrickRowsRb, kBrickBatchRowsHalf = kBrickRowsRb / 2;
+// `steps` (<= plan.halo) red-black iterations with the precise arithmetic on every field of d_fields[0 .. nfields) (a slot whose
+// bufs[0] is null is skipped), from each field's bufs[src] into its bufs[dst]; parity = number of the first iteration & 1; check: the
+// last step's max |du| per brick (nb0 x nb1 x nbc floats, plain stores: may be pinned host memory) goes to the fields' tile_delta.
+// capacity_rows: kBrickBatchRows or kBrickBatchRowsHalf, at least plan.s0 * plan.s1.  Kept out of the driver_* units (they are also
+// built against a stand-in runtime that does not have this launcher).
+hipError_t launch_brick_3d_batch(const BatchField *d_fields, int nfields, int src, int dst, int m0, int m1, int pitch, const BrickPlan &plan,
+                                 int capacity_rows, int steps, int parity, bool check, hipStream_t stream);
 
 // ---- consumers and edits of the resident 3-D field (field_3d.hip); called from field3d_driver.hip only ----------------
 // The 3-D masks are the 2-D lane masks over the m0 * m1 rows of m2 cells: word and bit of cell (x0, x1, x2) are

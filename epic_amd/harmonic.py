@@ -387,8 +387,8 @@ class Harmonic(eh.EpicHarmonic):
 def solve_batch(fields, numThreads=1024, epsilon=None):
     """Relax several ``Harmonic`` objects in ONE call (epic_hip_complete_batch_gpu): a field per robot, per candidate goal, per
     hypothesis, on one map.  Every field ends exactly as its own ``solve(process='gpu')`` would leave it; the fields that share a
-    shape and a checking period and are in the library's default mode advance together on the device, the others one after
-    another inside the call.  ``epsilon``: a scalar for all, one value per field, or None to keep each field's own.  Raises
+    shape and a checking period and are in the library's default mode advance together on the device (2-D maps on LDS tiles,
+    3-D voxel fields of one shape on LDS bricks, each from the field count at which that was measured faster), the others one after another inside the call.  ``epsilon``: a scalar for all, one value per field, or None to keep each field's own.  Raises
     ``RuntimeError`` naming the first field that failed and its code.  Returns (wall-time, cpu-time) of the call, like ``solve``."""
     fields = list(fields)
     if epsilon is not None:

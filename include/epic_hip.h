@@ -411,15 +411,25 @@ int epic_hip_config_reload(EpicHarmonicT *harmonic);
  * WHERE the iterations run: fields with n == 2 that share m and numIterationsToStaggerCheck, whose contexts are in the library's
  * default mode (precise math, red-black scheme, one device) on a grid the LDS tiles serve (epic_hip_tile_iterations > 0), advance
  * TOGETHER -- one launch for all of them, a workgroup holding the same tile of up to four fields (epic_amd/csrc/kernels_tile2d_batch.hip);
- * epsilon may differ per field.  Every other field (tol or fast math, Jacobi, 3-D, a shape of its own, fewer fields of a shape than the
- * measured crossover: two up to 0.25 Mcell, four above) runs through harmonic_execute_gpu inside the same call.  Both calls are ordering points for every field.  EPIC_HIP_BATCH=0: every field through harmonic_execute_gpu.
- * Study knobs: EPIC_HIP_BATCH_FIELDS (fields per workgroup: 1, 2, 4), EPIC_HIP_BATCH_HALO / _ROWS / _WIDTH (the tiles' geometry).
- * Measured against a loop of harmonic_complete_gpu: DESIGN.md section 4.13, profiles/batch_2d.txt. */
+ * epsilon may differ per field.  Fields with n == 3 are batched the same way: those that share all three extents and
+ * numIterationsToStaggerCheck, in the default mode on a grid the LDS bricks serve (epic_hip_brick_iterations > 0), advance together on
+ * bricks, one field per workgroup (epic_amd/csrc/kernels_brick3d_batch.hip) -- where that was measured faster than the loop: from four
+ * fields between 32^3 and 64^3 cells and above 64 x 64 x 200 up to 96^3, from two in between, never below 32^3 or above 96^3; a lone
+ * 3-D field is never batched.  Every other field
+ * (tol or fast math, Jacobi, a shape of its own, fewer 2-D fields of a shape than the measured crossover: two up to 0.25 Mcell, four
+ * above) runs through harmonic_execute_gpu inside the same call.  Both calls are ordering points for every field.  EPIC_HIP_BATCH=0:
+ * every field through harmonic_execute_gpu.
+ * Study knobs: EPIC_HIP_BATCH_FIELDS (fields per workgroup: 1, 2, 4), EPIC_HIP_BATCH_HALO / _ROWS / _WIDTH (the tiles' geometry); 3-D:
+ * EPIC_HIP_BATCH_HALO (shell depth), EPIC_HIP_BRICK_DIMS (S0xS1 of a brick), EPIC_HIP_BATCH_BRICK_ROWS = 288 | 576 (LDS capacity).
+ * Measured against a loop of harmonic_complete_gpu: DESIGN.md sections 4.13 and 4.14, profiles/batch_2d.txt, profiles/batch_3d.txt. */
 int epic_hip_execute_batch_gpu(EpicHarmonicT *const *fields, unsigned int count, unsigned int numThreads, int *results);
 int epic_hip_complete_batch_gpu(EpicHarmonicT *const *fields, unsigned int count, unsigned int numThreads, int *results);
 /* What the two calls above would do with these fields now: *batched = how many go through the batched kernel (0: none), and the
  * plan of the first group of them -- fields per workgroup, ghost rings = iterations per launch, owned rows and columns of a tile
- * (all 0 when nothing is batched).  Any output may be NULL.  The plan is made again whenever fields have left the batch. */
+ * (all 0 when nothing is batched).  *batched counts the members of 2-D and 3-D groups alike; the geometry is that of the first group
+ * in the caller's order.  For a 3-D group: fields_per_workgroup = 1, halo = shell depth = iterations per launch, tile_rows = S0 and
+ * tile_cols = S1, the planes and the rows (of 64 cells along x2) a brick holds, shells included.  Any output may be NULL.  The plan is
+ * made again whenever fields have left the batch. */
 int epic_hip_batch_plan(EpicHarmonicT *const *fields, unsigned int count, unsigned int *batched, int *fields_per_workgroup, int *halo,
                         int *tile_rows, int *tile_cols);
 
