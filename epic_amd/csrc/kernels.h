@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <vector>
+
 #include "driver_config.h"   // LaunchKnobs: what the launchers take from the environment (read in driver_config.cpp only)
 
 namespace epic_hip {
@@ -359,6 +361,26 @@ struct OccRegion {
 };
 hipError_t launch_occupancy_region(float *u, uint32_t *maskw, const unsigned char *d_occ, const OccRegion &region, int pitch,
                                    int obstacle_threshold, int no_change, unsigned flags, unsigned long long *d_changed, hipStream_t stream);
+
+// ---- Euclidean inflation of a block's obstacle bytes (occupancy_inflate.hip) -----------------------------------------------
+// The block of launch_occupancy_region on the device, extent[0] * extent[1] rows of extent[2] bytes, edited in place: every cell
+// within sqrt(radius_sq) (1 .. 256) of a source byte that is not a source itself gets the largest byte that is not no_change.
+// The plan is made on the host; d_scratch: 8-byte aligned device memory of plan.scratch_bytes() (the source bits, then the table).
+// upload_occupancy_inflate copies the table there (the plan must live until the stream has run the copy), launch_occupancy_inflate
+// enqueues the two kernels behind it.  Called from occupancy_driver.hip only.
+struct OccInflatePlan {
+    int extent[3];
+    unsigned radius_sq;
+    int nwords;              // 64-cell words per row
+    int tz, ty, hz, hy;      // a brick's planes and rows, the halo's
+    std::vector<int> table;  // per offset (dz, dy), the widest first: (LDS distance of the row) << 8 | half-width along x
+    size_t bits_bytes;
+    size_t scratch_bytes() const { return bits_bytes + table.size() * sizeof(int); }
+};
+OccInflatePlan plan_occupancy_inflate(const int extent[3], unsigned radius_sq);
+hipError_t upload_occupancy_inflate(const OccInflatePlan &plan, void *d_scratch, hipStream_t stream);
+hipError_t launch_occupancy_inflate(const OccInflatePlan &plan, unsigned char *d_occ, void *d_scratch, int obstacle_threshold, int no_change,
+                                    unsigned flags, hipStream_t stream);
 
 // ---- queries of the resident field (field_query.hip); called from field_query_driver.hip only ------------------------------
 // The field as the context holds it; a 2-D field is one plane: m0 = 1, m1 = rows.  Nothing is written to u or the masks.

@@ -93,6 +93,24 @@ int epic_hip_set_occupancy_region_cpu(Harmonic *h, const void *occ, const unsign
     return EPIC_SUCCESS;
 }
 
+// The inflated form (include/epic_hip.h: epic_hip_set_occupancy_inflated_*): the block B' by its definition (occupancy_rule.h:
+// occupancy_inflate_block), then the region walk above on B'.
+int epic_hip_set_occupancy_inflated_cpu(Harmonic *h, const void *occ, const unsigned int *origin, const unsigned int *extent,
+                                        int obstacle_threshold, int no_change, unsigned flags, unsigned int radius_sq,
+                                        unsigned long long *changed)
+{
+    size_t m[3], o[3], e[3];
+    if (radius_sq > EPIC_HIP_OCC_MAX_RADIUS_SQ || h == nullptr || h->m == nullptr || h->u == nullptr || h->locked == nullptr || occ == nullptr ||
+        !epic_hip::occupancy_region(h->n, h->m, origin, extent, m, o, e)) {
+        fprintf(stderr, "Error[epic_hip_set_occupancy_inflated_cpu]: %s\n", "Invalid data.");
+        return EPIC_ERROR_INVALID_DATA;
+    }
+    if (radius_sq == 0) return epic_hip_set_occupancy_region_cpu(h, occ, origin, extent, obstacle_threshold, no_change, flags, changed);
+    std::vector<unsigned char> inflated(e[0] * e[1] * e[2]);
+    epic_hip::occupancy_inflate_block(static_cast<const unsigned char *>(occ), e, obstacle_threshold, no_change, flags, radius_sq, inflated.data());
+    return epic_hip_set_occupancy_region_cpu(h, inflated.data(), origin, extent, obstacle_threshold, no_change, flags, changed);
+}
+
 int epic_hip_reset_free_cells_3d_cpu(Harmonic *h)
 {
     if (h == nullptr || h->m == nullptr || h->u == nullptr || h->locked == nullptr || h->n != 3) {

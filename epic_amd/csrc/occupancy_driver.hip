@@ -17,6 +17,13 @@
 // the same sequence on 2-D and 3-D fields with the launcher of occupancy_region.hip: only the region's bytes are copied.  The 3-D
 // sweeps derive nothing from the masks, so a 3-D edit rebuilds nothing.  In multi-device mode a 2-D region takes the list route
 // above, restricted to the window; a 3-D field lives in plane slabs there, for which no edit is built: the calls name the host route.
+//
+// The inflated form (epic_hip_set_occupancy_inflated_gpu) is the region form with one more step on the stream: between the upload of the
+// bytes and the region kernel the launchers of occupancy_inflate.hip edit the uploaded bytes in place, with their scratch (source bits,
+// offset table) behind the bytes in the same temporary.  kernel_ms then times that step.  On slabs a 2-D block is inflated on the host
+// (occupancy_rule.h: occupancy_inflate_block) and takes the list route; a 3-D field names the host route as above.
+#include <functional>
+
 #include "driver.h"
 #include "occupancy_rule.h"
 
@@ -98,9 +105,15 @@ int multi_dense_edit(Harmonic *h, Ctx *c, const unsigned char *occ, int obstacle
 // rows padded to the field's pitch was measured and gained nothing: profiles/occupancy_ingest.txt) --, launch(d_occ, d_changed), in 2-D
 // the fused masks, the counters back, synchronise, free, and force_all unless KEEP_FREE is set and nothing changed.
 // kernel_ms (may be null): the device time of the ingestion kernel alone, between two events on the context's stream
+// prepare (the inflated form; empty otherwise): a launch that edits the bytes on the device before `launch` reads them, with `extra`
+// bytes of scratch behind them (16-byte aligned).  Called twice: kernels == false for its uploads, then kernels == true between the
+// events, which then bracket prepare's kernels, not launch
+using Prepare = std::function<hipError_t(unsigned char *d_occ, void *d_scratch, bool kernels)>;
 template <class Launch>
-int staged_edit(Ctx *c, const void *occ, size_t bytes, unsigned flags, unsigned long long *changed, float *kernel_ms, const char *fn, Launch launch)
+int staged_edit(Ctx *c, const void *occ, size_t bytes, unsigned flags, unsigned long long *changed, float *kernel_ms, const char *fn, Launch launch,
+                size_t extra = 0, const Prepare &prepare = Prepare())
 {
+    const size_t scratch_at = (bytes + 15) & ~(size_t)15;
     const size_t slot = epic_hip::kOccCounterBytes;
     unsigned char *tmp = nullptr;
     unsigned long long count = 0;
@@ -112,7 +125,7 @@ int staged_edit(Ctx *c, const void *occ, size_t bytes, unsigned flags, unsigned 
         (void)hipGetLastError();
         report(fn, "Failed to create the timing events.");
         rc = EPIC_ERROR_DEVICE_MALLOC;
-    } else if (hipMalloc((void **)&tmp, slot + bytes) != hipSuccess) {
+    } else if (hipMalloc((void **)&tmp, slot + (extra ? scratch_at + extra : bytes)) != hipSuccess) {
         (void)hipGetLastError();
         report(fn, "Failed to allocate device-side memory for the occupancy image.");
         rc = EPIC_ERROR_DEVICE_MALLOC;
@@ -123,9 +136,11 @@ int staged_edit(Ctx *c, const void *occ, size_t bytes, unsigned flags, unsigned 
             hipMemcpyAsync(d_occ, occ, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
             report(fn, "Failed to copy memory from host to device for the occupancy image.");
             rc = EPIC_ERROR_MEMCPY_TO_DEVICE;
-        } else if ((kernel_ms && hipEventRecord(ev[0], c->stream) != hipSuccess) ||
+        } else if ((prepare && prepare(d_occ, d_occ + scratch_at, false) != hipSuccess) ||
+                   (kernel_ms && hipEventRecord(ev[0], c->stream) != hipSuccess) ||
+                   (prepare && (prepare(d_occ, d_occ + scratch_at, true) != hipSuccess || (kernel_ms && hipEventRecord(ev[1], c->stream) != hipSuccess))) ||
                    launch(d_occ, d_changed) != hipSuccess ||
-                   (kernel_ms && hipEventRecord(ev[1], c->stream) != hipSuccess) ||
+                   (kernel_ms && !prepare && hipEventRecord(ev[1], c->stream) != hipSuccess) ||
                    (c->n == 2 && epic_hip::launch_fuse_masks_2d(c->maskw, c->rows, c->pitch, c->maskf(), c->stream) != hipSuccess)) {
             report(fn, "Failed to execute the 'set occupancy' kernel.");
             rc = EPIC_ERROR_KERNEL_EXECUTION;
@@ -177,15 +192,18 @@ int set_occupancy(Harmonic *harmonic, const void *occ, int obstacle_threshold, i
 }
 
 const char *kMulti3dRegion = "Invalid data (not available in multi-device mode: use epic_hip_set_occupancy_region_cpu and harmonic_update_model_gpu).";
+const char *kMulti3dInflated = "Invalid data (not available in multi-device mode: use epic_hip_set_occupancy_inflated_cpu and harmonic_update_model_gpu).";
 const char *kMulti3dReset = "Invalid data (not available in multi-device mode: use epic_hip_reset_free_cells_3d_cpu and harmonic_update_model_gpu).";
 
 // The region form, n in {2, 3}: set_occupancy's ordering point and staged_edit, with only the region's bytes over the bus and only
 // the region's rows and strips under the kernel (occupancy_region.hip).
+// radius_sq != 0, the inflated form: the uploaded bytes are inflated in place (occupancy_inflate.hip) before the region kernel reads
+// them, and kernel_ms is the time of that; on slabs the host builds B' (occupancy_rule.h) for the 2-D list route.
 int set_occupancy_region(Harmonic *harmonic, const void *occ, const unsigned *origin, const unsigned *extent, int obstacle_threshold,
-                         int no_change, unsigned flags, unsigned long long *changed, float *kernel_ms, const char *fn)
+                         int no_change, unsigned flags, unsigned long long *changed, float *kernel_ms, const char *fn, unsigned radius_sq = 0)
 {
     size_t m[3], o[3], e[3];
-    const bool host_ok = harmonic != nullptr && harmonic->m != nullptr && harmonic->u != nullptr && harmonic->locked != nullptr &&
+    const bool host_ok = radius_sq <= EPIC_HIP_OCC_MAX_RADIUS_SQ && harmonic != nullptr && harmonic->m != nullptr && harmonic->u != nullptr && harmonic->locked != nullptr &&
                          occ != nullptr && epic_hip::occupancy_region(harmonic->n, harmonic->m, origin, extent, m, o, e);
     Ctx *c = host_ok ? find_ctx(harmonic) : nullptr;
     if (c == nullptr || !ready(harmonic, c) || c->n != (int)harmonic->n || !same_dims(harmonic, c)) {
@@ -193,7 +211,7 @@ int set_occupancy_region(Harmonic *harmonic, const void *occ, const unsigned *or
         return EPIC_ERROR_INVALID_DATA;
     }
     if (c->n == 3 && c->multi()) {  // plane slabs: edit the host arrays and upload them again
-        report(fn, kMulti3dRegion);
+        report(fn, radius_sq ? kMulti3dInflated : kMulti3dRegion);
         return EPIC_ERROR_INVALID_DATA;
     }
     {
@@ -203,7 +221,14 @@ int set_occupancy_region(Harmonic *harmonic, const void *occ, const unsigned *or
     if (kernel_ms) *kernel_ms = 0.0f;
     if (c->multi()) {
         const size_t win[4] = {o[1], o[2], e[1], e[2]};
-        return multi_dense_edit(harmonic, c, static_cast<const unsigned char *>(occ), obstacle_threshold, no_change, flags, changed, fn, win);
+        const unsigned char *bytes = static_cast<const unsigned char *>(occ);
+        std::vector<unsigned char> inflated;
+        if (radius_sq) {
+            inflated.resize(e[1] * e[2]);
+            epic_hip::occupancy_inflate_block(bytes, e, obstacle_threshold, no_change, flags, radius_sq, inflated.data());
+            bytes = inflated.data();
+        }
+        return multi_dense_edit(harmonic, c, bytes, obstacle_threshold, no_change, flags, changed, fn, win);
     }
 
     epic_hip::OccRegion region;
@@ -215,10 +240,17 @@ int set_occupancy_region(Harmonic *harmonic, const void *occ, const unsigned *or
         region.extent[a] = (int)e[a];
     }
     region.faces0 = c->n == 3;
-    return staged_edit(c, occ, e[0] * e[1] * e[2], flags, changed, kernel_ms, fn, [&](const unsigned char *d_occ, unsigned long long *d_changed) {
+    const auto ingest = [&](const unsigned char *d_occ, unsigned long long *d_changed) {
         return epic_hip::launch_occupancy_region(c->buf[c->cur], c->maskw, d_occ, region, c->pitch, obstacle_threshold, no_change, flags, d_changed,
                                                  c->stream);
-    });
+    };
+    if (radius_sq == 0) return staged_edit(c, occ, e[0] * e[1] * e[2], flags, changed, kernel_ms, fn, ingest);
+    const epic_hip::OccInflatePlan plan = epic_hip::plan_occupancy_inflate(region.extent, radius_sq);   // lives until staged_edit has synchronised
+    return staged_edit(c, occ, e[0] * e[1] * e[2], flags, changed, kernel_ms, fn, ingest, plan.scratch_bytes(),
+                       [&](unsigned char *d_occ, void *d_scratch, bool kernels) {
+                           return kernels ? epic_hip::launch_occupancy_inflate(plan, d_occ, d_scratch, obstacle_threshold, no_change, flags, c->stream)
+                                          : epic_hip::upload_occupancy_inflate(plan, d_scratch, c->stream);
+                       });
 }
 
 }  // namespace
@@ -288,6 +320,19 @@ int epic_hip_timed_occupancy_region_gpu(Harmonic *harmonic, const void *occ, con
         return EPIC_ERROR_INVALID_DATA;
     }
     return set_occupancy_region(harmonic, occ, origin, extent, obstacle_threshold, no_change, flags, changed, kernel_ms, fn);
+}
+
+// radius_sq == 0 is the region call; no inflation kernel runs and *kernel_ms is 0
+int epic_hip_set_occupancy_inflated_gpu(Harmonic *harmonic, const void *occ, const unsigned int *origin, const unsigned int *extent,
+                                        int obstacle_threshold, int no_change, unsigned flags, unsigned int radius_sq,
+                                        unsigned long long *changed, float *kernel_ms)
+{
+    static const char *fn = "epic_hip_set_occupancy_inflated_gpu";
+    float ms = 0.0f;
+    const int rc = set_occupancy_region(harmonic, occ, origin, extent, obstacle_threshold, no_change, flags, changed,
+                                        kernel_ms && radius_sq ? &ms : nullptr, fn, radius_sq);
+    if (rc == EPIC_SUCCESS && kernel_ms) *kernel_ms = ms;
+    return rc;
 }
 
 // unlocked cells are interior cells (the faces and the padding are locked in the masks), and the 3-D masks are the 2-D lane masks

@@ -1,8 +1,13 @@
 // occupancy_rule.h -- the per-cell rule of the dense occupancy ingestion (include/epic_hip.h: epic_hip_set_occupancy_2d_*), stated
 // once for the host walk (occupancy_cpu.cpp) and the kernels (occupancy_2d.hip, occupancy_region.hip).  Interior cells only: the
-// callers never hand a border cell in.
+// callers never hand a border cell in.  Below it, host only: the region's geometry, and the inflated block B' of
+// epic_hip_set_occupancy_inflated_* by its definition (the CPU twin's and the multi-device route's; the kernel of occupancy_inflate.hip
+// is held to it).
 #pragma once
 #include <string.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "../../include/epic/epic_abi.h"
 #include "../../include/epic_hip.h"
@@ -76,6 +81,53 @@ inline bool occupancy_region(unsigned n, const unsigned *m, const unsigned *orig
         e[lead + i] = ei;
     }
     return true;
+}
+
+// The inflated block B' of epic_hip_set_occupancy_inflated_* by its definition, on the host: `out` (e[0] * e[1] * e[2] bytes) is the
+// block with every cell within sqrt(radius_sq) of a source, and not a source itself, set to X.  The squared distance to the nearest
+// source of the block is the minimum over the sources of a sum of three squares, taken axis by axis: along the fastest axis first
+// (a walk up and a walk down every row), then the minimum over the rows dy away of that plus dy^2, then over the planes.  Integers;
+// everything above radius_sq is held at radius_sq + 1 ("far"), so 16 bits hold it (radius_sq <= 256).
+inline void occupancy_inflate_block(const unsigned char *block, const size_t e[3], int obstacle_threshold, int no_change, unsigned flags,
+                                    unsigned radius_sq, unsigned char *out)
+{
+    const size_t cells = e[0] * e[1] * e[2];
+    const unsigned far = radius_sq + 1;
+    const int top = (flags & EPIC_HIP_OCC_UNSIGNED) ? 255 : 127;
+    const unsigned char fill = (unsigned char)(top == no_change ? top - 1 : top);
+    long reach = 0;
+    while ((reach + 1) * (reach + 1) <= (long)radius_sq) reach++;
+    auto source = [&](size_t i) {
+        const int v = (flags & EPIC_HIP_OCC_UNSIGNED) ? (int)block[i] : (int)(signed char)block[i];
+        return v != no_change && v >= obstacle_threshold;
+    };
+    std::vector<unsigned short> d(cells), next(cells);
+    for (size_t row = 0; row < e[0] * e[1]; row++) {   // along a row: the distance to the nearest source on either side, squared
+        unsigned short *dr = d.data() + row * e[2];
+        unsigned gap = far;   // cells since the last source; far: none yet (far * far > radius_sq)
+        for (size_t x = 0; x < e[2]; x++) {
+            gap = source(row * e[2] + x) ? 0u : std::min(gap + 1u, far);
+            dr[x] = (unsigned short)std::min(gap * gap, far);
+        }
+        gap = far;
+        for (size_t x = e[2]; x-- > 0;) {
+            gap = source(row * e[2] + x) ? 0u : std::min(gap + 1u, far);
+            dr[x] = (unsigned short)std::min<unsigned>(dr[x], std::min(gap * gap, far));
+        }
+    }
+    for (int axis = 1; axis >= 0; axis--) {   // then across the rows of a plane, then across the planes
+        const size_t count = e[axis], stride = axis == 1 ? e[2] : e[1] * e[2];
+        if (count == 1) continue;
+        for (size_t i = 0; i < cells; i++) {
+            const long at = (long)((i / stride) % count);
+            unsigned best = far;
+            for (long k = std::max(-reach, -at); k <= reach && at + k < (long)count; k++)
+                best = std::min(best, (unsigned)d[(size_t)((long)i + k * (long)stride)] + (unsigned)(k * k));
+            next[i] = (unsigned short)std::min(best, far);
+        }
+        d.swap(next);
+    }
+    for (size_t i = 0; i < cells; i++) out[i] = (d[i] <= radius_sq && !source(i)) ? fill : block[i];
 }
 
 }  // namespace epic_hip

@@ -158,6 +158,10 @@ _SIGNATURES = {
     "epic_hip_set_occupancy_region_gpu": (_H, ct.c_void_p, _UP, _UP, ct.c_int, ct.c_int, ct.c_uint, ct.POINTER(ct.c_ulonglong)),
     "epic_hip_timed_occupancy_region_gpu": (_H, ct.c_void_p, _UP, _UP, ct.c_int, ct.c_int, ct.c_uint, ct.POINTER(ct.c_ulonglong),
                                             ct.POINTER(ct.c_float)),
+    # the region calls with Euclidean inflation of the block's obstacle bytes in front (radius_sq <= 256)
+    "epic_hip_set_occupancy_inflated_cpu": (_H, ct.c_void_p, _UP, _UP, ct.c_int, ct.c_int, ct.c_uint, ct.c_uint, ct.POINTER(ct.c_ulonglong)),
+    "epic_hip_set_occupancy_inflated_gpu": (_H, ct.c_void_p, _UP, _UP, ct.c_int, ct.c_int, ct.c_uint, ct.c_uint, ct.POINTER(ct.c_ulonglong),
+                                            ct.POINTER(ct.c_float)),
     "epic_hip_reset_free_cells_3d_cpu": (_H,),
     "epic_hip_reset_free_cells_3d_gpu": (_H,),
     # field queries: points are n floats each, cell lists n unsigned each, origin / extent n entries in the order of m

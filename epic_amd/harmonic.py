@@ -108,7 +108,7 @@ class Harmonic(eh.EpicHarmonic):
 
     # -- map messages ---------------------------------------------------------------------------------------
     def set_occupancy(self, occ, obstacle_threshold=50, no_change=-2, keep_free=False, unsigned=False, over_goals=False,
-                      process='gpu', origin=None):
+                      process='gpu', origin=None, inflate_sq=0):
         """Apply a map message (one byte per cell, shape m) by the rule of epic_hip_set_occupancy_2d_* (include/epic_hip.h):
         the defaults are the navigation node's /map callback; ``unsigned=True, over_goals=True, obstacle_threshold=250,
         no_change=-1`` is the nav_core plugin's costmap rule.  ``process``: 'cpu' edits the host arrays, 'gpu' the
@@ -117,7 +117,11 @@ class Harmonic(eh.EpicHarmonic):
 
         The grid may be 2-D or 3-D.  ``origin`` (n entries in the order of m, slowest axis first) makes ``occ`` a window of
         a map or a box of voxels placed there, ``occ.shape`` being its extent (epic_hip_set_occupancy_region_*); the
-        window must lie inside the grid."""
+        window must lie inside the grid.
+
+        ``inflate_sq`` > 0 (at most 256) grows the obstacle bytes of ``occ`` first: every cell within sqrt(inflate_sq) cells
+        of an obstacle byte of the block becomes an obstacle (epic_hip_set_occupancy_inflated_*).  Inflation stops at the
+        block's edge: a window needs a margin of ceil(sqrt(inflate_sq)) cells around what changed."""
         if process not in ('gpu', 'cpu', 'both'):
             raise ValueError("process must be 'gpu', 'cpu' or 'both'")
         n = int(self.n)
@@ -145,9 +149,14 @@ class Harmonic(eh.EpicHarmonic):
             window = (origin.ctypes.data_as(UP), extent.ctypes.data_as(UP))
             variants = ((eh._epic.epic_hip_set_occupancy_region_cpu, window), (eh._epic.epic_hip_set_occupancy_region_gpu, window))
         changed = ct.c_ulonglong(0)
+        if inflate_sq:
+            where = variants[0][1] or (None, None)
+            rule += (int(inflate_sq),)
+            variants = ((eh._epic.epic_hip_set_occupancy_inflated_cpu, where), (eh._epic.epic_hip_set_occupancy_inflated_gpu, where))
         for (variant, where), wanted in zip(variants, (('cpu', 'both'), ('gpu', 'both'))):
             if process in wanted:
-                rc = variant(self, occ.ctypes.data, *where, *rule, ct.byref(changed))
+                tail = (None,) if variant is eh._epic.epic_hip_set_occupancy_inflated_gpu else ()   # kernel_ms
+                rc = variant(self, occ.ctypes.data, *where, *rule, ct.byref(changed), *tail)
                 if rc != 0:
                     raise RuntimeError("epic_amd: %s failed with code %d" % (variant.__name__, rc))
         return int(changed.value)

@@ -268,6 +268,36 @@ int epic_hip_timed_occupancy_region_gpu(EpicHarmonicT *h, const void *occ, const
 int epic_hip_reset_free_cells_3d_cpu(EpicHarmonicT *h);
 int epic_hip_reset_free_cells_3d_gpu(EpicHarmonicT *h);
 
+/* ---- obstacle inflation in front of the region calls, 2-D and 3-D ----------------------------------------------------
+ * A potential field plans for a point: a caller grows the obstacles by the robot's radius first (costmap_2d's inflation layer on
+ * the CPU; for a box of raw voxels nothing did).  These are epic_hip_set_occupancy_region_* with exact Euclidean inflation of the
+ * block's obstacle bytes in front: occ, origin, extent, obstacle_threshold, no_change, flags and changed mean what they mean there.
+ * With v(c) the byte of block cell c widened as flags says:
+ *   1. sources   S = { c in the block : v(c) != no_change and v(c) >= obstacle_threshold } -- the bytes only, not the resident state;
+ *   2. near(c)   some s in S has sum_i (c_i - s_i)^2 <= radius_sq: block coordinates, every axis of m, integers.  Only sources
+ *                inside the block count and inflation stops at the block's edge: A CALLER WHO UPDATES A WINDOW PASSES A MARGIN OF
+ *                ceil(sqrt(radius_sq)) CELLS around what changed, or obstacles just outside the window do not reach into it;
+ *   3. B'(c) = X where near(c) and c is not in S, B(c) everywhere else; X is the largest value of the byte type (127 signed, 255
+ *                unsigned), or one less where that equals no_change -- an obstacle byte that is not no_change whenever S is not
+ *                empty.  A near cell becomes an obstacle even if its own byte was no_change or "unknown"; a goal inside the radius
+ *                survives unless EPIC_HIP_OCC_OVER_GOALS is set (step 2 of the rule);
+ *   4. the result is that of epic_hip_set_occupancy_region_* for B' with the same arguments: u, the lock state, *changed, the cells
+ *                never touched, the ordering point, and what EPIC_HIP_OCC_KEEP_FREE with *changed == 0 promises.
+ * radius_sq == 0 is the region call, bit for bit.  radius_sq > EPIC_HIP_OCC_MAX_RADIUS_SQ (more than 16 cells) returns
+ * EPIC_ERROR_INVALID_DATA with nothing touched; every other error code is the region call's for the same cause.
+ * The _gpu variant inflates on the device, between the upload of the block and the ingestion kernel (occupancy_inflate.hip: source
+ * bits by ballot, dilation of 64 cells at a time in LDS); *kernel_ms (may be NULL) receives the device time of the inflation
+ * kernels alone, 0 where none ran (radius_sq == 0, multi-device mode).  Multi-device mode: a 2-D block is inflated on the host and
+ * takes the region call's route there, bit-identical to one device; for n == 3 the call returns EPIC_ERROR_INVALID_DATA with a
+ * message naming the host route, epic_hip_set_occupancy_inflated_cpu followed by harmonic_update_model_gpu. */
+#define EPIC_HIP_OCC_MAX_RADIUS_SQ 256u
+int epic_hip_set_occupancy_inflated_cpu(EpicHarmonicT *h, const void *occ, const unsigned int *origin, const unsigned int *extent,
+                                        int obstacle_threshold, int no_change, unsigned flags, unsigned int radius_sq,
+                                        unsigned long long *changed);
+int epic_hip_set_occupancy_inflated_gpu(EpicHarmonicT *h, const void *occ, const unsigned int *origin, const unsigned int *extent,
+                                        int obstacle_threshold, int no_change, unsigned flags, unsigned int radius_sq,
+                                        unsigned long long *changed, float *kernel_ms /* may be NULL */);
+
 /* ---- Field queries: point samples, flow fields, cell read-back (2-D and 3-D) -----------------------------------------
  * Questions a caller asks of a relaxed field, answered where the field lives: harmonic->n is 2 or 3, and every call dispatches
  * on it.  The reference answers a request for one value by copying the whole field to the host

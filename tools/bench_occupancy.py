@@ -15,7 +15,11 @@ previous state (the state is uploaded again before each call, untimed), so every
 256^2 window of an 8192^2 map, each against the routes it replaces in the same run (run_region: the list route, the host edit followed
 by harmonic_update_model_gpu, and for the 2-D window the whole-image call).  The 512^3 grid needs about 10 GB of host memory.
 
-    python tools/bench_occupancy.py [--sizes 1024 8192] [--regions vox512 box64 win256] [--calls 20] [--warmup 3] [--out profiles/occupancy_ingest.txt]
+--inflate map1024 map8192 win256 vox64 vox128 vox512: epic_hip_set_occupancy_inflated_gpu at radius_sq 9, 64 and 256 against the only
+route a caller had before it -- dilate the block on the host, then epic_hip_set_occupancy_region_gpu (run_inflate).
+
+    python tools/bench_occupancy.py [--sizes 1024 8192] [--regions vox512 box64 win256] [--inflate map1024 ...] [--calls 20] [--warmup 3]
+                                    [--out profiles/occupancy_ingest.txt]
 """
 import argparse
 import ctypes as ct
@@ -219,12 +223,81 @@ def run_region(name):
                med["kernel"], med["list"] / med["region"], med["host"] / med["region"]))
 
 
+INFLATE = {   # name: (grid, origin, extent, calls, warm-up calls); the host route of a 512^3 block takes seconds: fewer calls
+    "map1024": ([1024, 1024], None, None, 20, 3),
+    "map8192": ([8192, 8192], None, None, 5, 1),
+    "win256": ([8192, 8192], (4000, 4000), (256, 256), 20, 3),
+    "vox64": ([64, 64, 64], None, None, 20, 3),
+    "vox128": ([128, 128, 128], None, None, 10, 2),
+    "vox512": ([512, 512, 512], None, None, 3, 1),
+}
+
+
+def run_inflate(name, radii=(9, 64, 256)):
+    """epic_hip_set_occupancy_inflated_gpu on one block, a line per radius_sq, every call on the same previous state:
+      host      the route without it: the block dilated on the host -- timed as epic_hip_set_occupancy_inflated_cpu on a host copy of the
+                region's cells, which builds B' and walks it once --, then epic_hip_set_occupancy_region_gpu (timed on the same bytes)
+      device    wall time of epic_hip_set_occupancy_inflated_gpu
+      inflate   *kernel_ms of that call: the two inflation kernels alone
+      ingest    the ingestion kernel alone at radius 0 (epic_hip_timed_occupancy_region_gpu)"""
+    m, origin, extent, calls, warmup = INFLATE[name]
+    n = len(m)
+    origin, extent = origin or (0,) * n, extent or tuple(m)
+    u0, l0 = synthetic_grid(m, 20240601, 0.05)
+    sl = tuple(slice(o, o + e) for o, e in zip(origin, extent))
+    occ = np.ascontiguousarray(message(m, l0)[sl])
+    print("# inflate %s: grid %s, block %s at %s, state and message built" % (name, "x".join(map(str, m)), "x".join(map(str, extent)), origin), flush=True)
+    h = Harmonic()
+    h.set_grid(m, u0, l0)
+    for fn in (E.harmonic_initialize_dimension_size_gpu, E.harmonic_initialize_potential_values_gpu, E.harmonic_initialize_locked_gpu):
+        assert fn(h) == 0, fn.__name__
+    assert E.harmonic_initialize_gpu(h, NT) == 0
+    side = Harmonic()   # the region's cells alone on the host: the block as a whole grid
+    side.set_grid(list(extent), u0.reshape(m)[sl], l0.reshape(m)[sl])
+    changed, ms = ct.c_ulonglong(0), ct.c_float(0.0)
+    o, e = (ct.c_uint * n)(*origin), (ct.c_uint * n)(*extent)
+    rule = (50, -2, 0)
+    out = []
+    for r2 in radii:
+        t = {key: [] for key in ("host", "region", "device", "inflate", "ingest")}
+        for i in range(warmup + calls):
+            t0 = time.perf_counter()
+            assert E.epic_hip_set_occupancy_inflated_cpu(side, occ.ctypes.data, None, None, *rule, r2, None) == 0
+            t1 = time.perf_counter()
+            assert E.harmonic_update_model_gpu(h) == 0   # the previous state again (untimed)
+            t2 = time.perf_counter()
+            assert E.epic_hip_set_occupancy_region_gpu(h, occ.ctypes.data, o, e, *rule, None) == 0
+            t3 = time.perf_counter()
+            assert E.harmonic_update_model_gpu(h) == 0
+            assert E.epic_hip_timed_occupancy_region_gpu(h, occ.ctypes.data, o, e, *rule, None, ct.byref(ms)) == 0
+            ingest = ms.value
+            assert E.harmonic_update_model_gpu(h) == 0
+            t4 = time.perf_counter()
+            assert E.epic_hip_set_occupancy_inflated_gpu(h, occ.ctypes.data, o, e, *rule, r2, ct.byref(changed), ct.byref(ms)) == 0
+            t5 = time.perf_counter()
+            if i >= warmup:
+                for key, value in (("host", t1 - t0), ("region", t3 - t2), ("device", t5 - t4), ("inflate", ms.value * 1e-3), ("ingest", ingest * 1e-3)):
+                    t[key].append(value)
+            print("# inflate %s radius_sq %d: call %d of %d" % (name, r2, i + 1, warmup + calls), flush=True)
+        med = {key: median_ms(value) for key, value in t.items()}
+        out.append("inflate %-7s %s, block %s, radius_sq %3d (%d calls after %d)  changed %9d | host route %10.3f ms (dilating on the host %10.3f ms + "
+                   "region_gpu %8.3f ms) | device route %8.3f ms | inflation kernels %8.4f ms | ingestion kernel (radius 0) %7.4f ms | host / device %.1fx"
+                   % (name, "x".join(map(str, m)), "x".join(map(str, extent)), r2, calls, warmup, changed.value, med["host"] + med["region"], med["host"],
+                      med["region"], med["device"], med["inflate"], med["ingest"], (med["host"] + med["region"]) / med["device"]))
+    for fn in (E.harmonic_uninitialize_gpu, E.harmonic_uninitialize_dimension_size_gpu, E.harmonic_uninitialize_potential_values_gpu,
+               E.harmonic_uninitialize_locked_gpu):
+        assert fn(h) == 0, fn.__name__
+    return "\n".join(out)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", type=int, nargs="*", default=[1024, 8192])
     ap.add_argument("--regions", nargs="*", choices=sorted(REGIONS), default=[],
                     help="region cases (epic_hip_set_occupancy_region_*): vox512 a whole 512^3 grid, box64 a 64^3 box in 512^3, "
                          "win256 a 256^2 window in 8192^2; each against the routes it replaces (run_region)")
+    ap.add_argument("--inflate", nargs="*", choices=sorted(INFLATE), default=[],
+                    help="epic_hip_set_occupancy_inflated_gpu at radius_sq 9, 64, 256 against dilating on the host (run_inflate)")
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None, help="also append the lines to this file")
@@ -238,7 +311,8 @@ def main():
         E.epic_hip_version().decode(), args.calls, args.warmup)
     print(head, flush=True)
     lines = [head]
-    jobs = [lambda n=n: run(n, args.calls, args.warmup) for n in args.sizes] + [lambda r=r: run_region(r) for r in args.regions]
+    jobs = [lambda n=n: run(n, args.calls, args.warmup) for n in args.sizes] + [lambda r=r: run_region(r) for r in args.regions] + [
+        lambda r=r: run_inflate(r) for r in args.inflate]
     for job in jobs:
         lines.append((args.label + " " if args.label else "") + job())
         print(lines[-1], flush=True)
