@@ -8,9 +8,11 @@
 // currentIteration = 0, harmonic_initialize_gpu), the same iterations in the same order with the same arithmetic, the reference's exit
 // rule (a converged check with currentIteration >= max(m)), the same end (harmonic_get_potential_values_gpu, harmonic_uninitialize_gpu)
 // -- so u, currentIteration, delta and the released device state are the single call's bit for bit.  Only WHERE the iterations run
-// differs: the fields that share a shape and a checking period and are in the library's default mode (precise, red-black, a grid the
-// single-field tile path -- 3-D: the single-field brick path -- takes) advance together, one launch for all of them; every other
-// field goes through harmonic_execute_gpu inside the same call.
+// differs: the fields that share a shape, a checking period and a mode (arithmetic, scheme, EPIC_HIP_JACOBI_CHECKS) on a grid the
+// single-field tile path -- 3-D: the single-field brick path, default mode only -- takes advance together, one launch for all of them;
+// every other field goes through harmonic_execute_gpu inside the same call.  A field whose check changes its mode (the tol mode's
+// finishing phase, the Jacobi hand-over: driver_loop.hip) leaves its group AT THAT CHECK, in the state its single call has there, and
+// goes on alone through harmonic_execute_gpu's own loop (relax_to_end).
 #include "driver.h"
 
 using namespace epic_drv;
@@ -22,23 +24,31 @@ struct Member {
     Harmonic *h;
     Ctx *c;
     unsigned index;   // in the caller's array
-    unsigned m_max;   // max(m): no exit before this many iterations (harmonic_gpu.cu:266)
+    std::shared_ptr<Relaxation> rx;   // from the start of its relaxation (run_group) until it has left the group and ended
 };
 struct BatchPlan { epic_hip::TilePlan tp; int fields; };   // fields per workgroup; 0: no plan
 struct BrickBatchPlan { epic_hip::BrickPlan bp; int capacity; };   // 3-D: the bricks and the LDS capacity (rows) of the instantiation; 0: no plan
 constexpr long long kBrickDeltaCap = 4096;   // bricks of a launch (their maxima are read per field after every block)
 
-// A field the batched kernel can take: everything harmonic_execute_gpu validates holds, and the context is in the library's
-// default mode on a grid the single-field tile path would take with its per-tile checks -- or, 3-D, one the single-field path
-// would put on bricks (which leaves out tracked contexts and grids above brick_up_to_cells).
+// Fields one workgroup holds of a tile of this mode and width: the library's default mode is kernels_tile2d_batch.hip, every other
+// arithmetic and scheme kernels_tile2d_batch_modes.hip; 0: no instantiation.
+bool default_mode(const Ctx *c) { return c->math == 0 && c->redblack; }
+int mode_max_fields(int math, bool redblack, int width)
+{
+    return math == 0 && redblack ? epic_hip::tile_2d_batch_max_fields(width) : epic_hip::tile_2d_batch_modes_max_fields(math, redblack, width);
+}
+
+// A field the batched kernel can take: everything harmonic_execute_gpu validates holds, and the context is in a mode that has a
+// batched instantiation, on a grid the single-field tile path would take with its per-tile checks -- or, 3-D, in the library's default
+// mode on a grid the single-field path would put on bricks (which leaves out tracked contexts and grids above brick_up_to_cells).
 bool batchable(Harmonic *h, Ctx *c)
 {
     if (!h || !h->m || !h->u || !h->locked || !(h->epsilon > 0.0f) || !h->d_m || !h->d_u || !h->d_locked || h->d_delta ||
         h->numIterationsToStaggerCheck == 0)
         return false;
     if (!ready(h, c) || (c->n != 2 && c->n != 3) || c->multi() || !c->devices.empty() || !c->cfg.batch || !c->cfg.tile_pipeline) return false;
-    if (c->math != 0 || !c->redblack) return false;
-    if (c->n == 3) return brick_plan(c).halo > 0;
+    if (c->n == 3) return default_mode(c) && brick_plan(c).halo > 0;
+    if (mode_max_fields(c->math, c->redblack, epic_hip::kTile2dCols) == 0) return false;
     return tile_checks(c, tile_plan(c));
 }
 
@@ -47,7 +57,20 @@ bool batchable(Harmonic *h, Ctx *c)
 // harmonic_complete_gpu in one process, three alternating repetitions; the rows "F=1 ... 2" are the plan two fields get): two fields
 // win about 1.4 x on basic.png (0.07 Mcell) and on maze.png (0.23 Mcell) and LOSE on umass.png (0.29 Mcell, about 0.9 x); from four
 // fields every map wins, 1.4 x and more.  Between 0.23 and 0.29 Mcell nothing was measured: the bound sits under umass.
-unsigned batch_from_fields(long long cells) { return cells > 250000 ? 4 : 2; }
+// The other modes, from profiles/batch_2d_modes.txt (the same tool and rule, the batch forced against a loop of harmonic_complete_gpu in
+// the same mode, epsilon 1e-3: on only where a row beats the loop by more than its spread).  Two fields: maze.png wins in every mode
+// (1.19-1.24 x), basic.png's 1.11-1.33 x lie inside spreads of 18-20 %, umass.png LOSES (0.95, 0.94, 0.78 x): not taken.  Four fields:
+//   tol red-black    1.21 / 1.31 / 1.14 x on basic / maze / umass (spread <= 1.3 %), 1.15-1.53 x at 16 and 64
+//   tol Jacobi       1.22 / 1.26 x on basic / maze; umass 1.02 x (spread 1.0 %) at four and 1.10-1.11 x from sixteen: above 0.25 Mcell from sixteen
+//   precise Jacobi   1.68 / 1.29 / 1.18 x, 1.32-1.72 x at 16 and 64
+//   fast             not measured: off (EPIC_HIP_BATCH=1 under EPIC_HIP_STUDY=1 takes it, as it takes any mode from two fields)
+unsigned batch_from_fields(const Ctx *c)
+{
+    const long long cells = (long long)c->rows * c->cols;
+    if (default_mode(c)) return cells > 250000 ? 4 : 2;
+    if (c->math == 4) return !c->redblack && cells > 250000 ? 16 : 4;
+    return c->math == 0 ? 4 : ~0u;
+}
 
 // Width, ring depth, tile height and fields per workgroup for `live` fields of rows x cols cells, by the cost model of the
 // single-field tiles (driver_plan.hip: tile_plan): an iteration of ONE workgroup costs its share of the launch,
@@ -63,18 +86,26 @@ unsigned batch_from_fields(long long cells) { return cells > 250000 ? 4 : 2; }
 // 1.23 / 1.27 x at 8 fields of umass.png, but 0.93 x and 0.96 x at 32 fields of maze.png and umass.png, where F = 1 needs many rounds:
 // 1.12 is basic.png's figure, not fitted further, and the model never picks F = 4 on the measured maps.
 // The bits do not depend on any of it.  Study knobs: EPIC_HIP_BATCH_FIELDS / _HALO / _ROWS / _WIDTH.
+// The other modes (math, redblack) take the same model with what differs in tile_plan's: a Jacobi wave takes a row per pass, not a row
+// pair, the tol passes issue in 0.17 us instead of 0.21, and the tile heights and fields per workgroup are what that mode's LDS holds
+// (kernels_tile2d_batch_modes.hip).  kStepOfFields is the precise red-black figure there too; the forced rows of
+// profiles/batch_2d_modes.txt say what F = 2 and F = 4 are worth with the tol table staged once for F fields.
 constexpr double kStepOfFields[5] = {0.0, 1.0, 1.04, 0.0, 1.12};   // [F]: step of a workgroup of F fields / (F x the step of one)
-BatchPlan batch_plan(int rows, int cols, unsigned live, const Config &cfg)
+BatchPlan batch_plan(int rows, int cols, unsigned live, const Config &cfg, int math = 0, bool redblack = true)
 {
     BatchPlan best = {{0, 0, 0, 0, 0}, 0};
     double best_cost = 0.0;
+    int widest_fields = 0;   // the most fields any allowed width holds in this mode: a forced F above it means that many
+    for (int width : {epic_hip::kTile2dCols, epic_hip::kTile2dWideCols})
+        if (!cfg.batch_width || width == cfg.batch_width) widest_fields = std::max(widest_fields, mode_max_fields(math, redblack, width));
     for (int width : {epic_hip::kTile2dCols, epic_hip::kTile2dWideCols}) {
         if (cfg.batch_width && width != cfg.batch_width) continue;
-        const int max_rows = epic_hip::tile_2d_max_rows(0, true, width), max_fields = epic_hip::tile_2d_batch_max_fields(width);
+        const int max_rows = epic_hip::tile_2d_max_rows(math, redblack, width), max_fields = mode_max_fields(math, redblack, width);
+        if (max_rows == 0) continue;
         for (int fields : {1, 2, 4}) {
             if (fields > max_fields) continue;
-            // a forced F means F: a width that cannot hold it is left out, unless the width is forced too (then its largest F)
-            if (cfg.batch_fields && fields != (cfg.batch_width ? std::min(cfg.batch_fields, max_fields) : cfg.batch_fields)) continue;
+            // a forced F means F: a width that cannot hold it is left out, unless no allowed width holds it (then the largest F there is)
+            if (cfg.batch_fields && fields != std::min(cfg.batch_fields, widest_fields)) continue;
             const int groups = (int)((live + fields - 1) / fields);
             for (int halo : {8, 10, 12, 14, 16}) {
                 const int h = cfg.batch_halo ? cfg.batch_halo : halo;
@@ -88,9 +119,9 @@ BatchPlan batch_plan(int rows, int cols, unsigned live, const Config &cfg)
                 const epic_hip::TilePlan p = epic_hip::tile_2d_plan(rows, cols, h, tr, width, max_rows);
                 if (p.halo > 0 && (size_t)p.tiles_r * p.tiles_c <= kTileDeltaCap) {
                     const int s_r = p.tile_rows + 2 * h;
-                    const double per_simd = s_r / 2.0 * (width / 64) / 4.0 * fields;
+                    const double per_simd = (redblack ? s_r / 2.0 : (double)s_r) * (width / 64) / 4.0 * fields;
                     const double rounds = std::max(1.0, (double)p.tiles_r * p.tiles_c * groups / 256.0);
-                    const double step = std::max(0.84 + 0.055 * per_simd, 0.2 + 0.21 * per_simd) * kStepOfFields[fields];
+                    const double step = std::max(0.84 + 0.055 * per_simd, 0.2 + (math == 4 ? 0.17 : 0.21) * per_simd) * kStepOfFields[fields];
                     const double cost = (rounds > 1.0 ? 1.6 * rounds / 2.0 + 0.2 : 1.0) * ((2.7 + 0.00006 * s_r * width * fields) / h + step);
                     if (best.fields == 0 || cost < best_cost) { best = BatchPlan{p, fields}; best_cost = cost; }
                 }
@@ -165,7 +196,8 @@ BrickBatchPlan batch_brick_plan(const int *m, unsigned live, const Config &cfg)
 }
 
 // What a batch call does with the fields as they are now: rc[i] = -1 for a field that goes through harmonic_execute_gpu; the
-// others in groups of one shape and one checking period, each at least batch_from_fields() strong, in the order of their first member.
+// others in groups of one shape, one checking period and one mode, each at least batch_from_fields() strong, in the order of their
+// first member (fields of different modes in one call form different groups; a lone field of its mode is never batched).
 std::vector<std::vector<Member>> group_fields(EpicHarmonicT *const *fields, unsigned count)
 {
     std::vector<std::vector<Member>> groups;
@@ -173,10 +205,11 @@ std::vector<std::vector<Member>> group_fields(EpicHarmonicT *const *fields, unsi
         Harmonic *h = fields[i];
         Ctx *c = h ? find_ctx(h) : nullptr;
         if (!batchable(h, c)) continue;
-        const Member m = {h, c, i, std::max(std::max(h->m[0], h->m[1]), c->n == 3 ? h->m[2] : 0u)};
+        const Member m = {h, c, i, nullptr};
         auto same = [&](const std::vector<Member> &g) {   // (3-D: rows = m[0] m[1], so all three extents are compared)
             return g[0].c->n == c->n && g[0].c->m[0] == c->m[0] && g[0].c->rows == c->rows && g[0].c->cols == c->cols &&
-                   g[0].h->numIterationsToStaggerCheck == h->numIterationsToStaggerCheck;
+                   g[0].h->numIterationsToStaggerCheck == h->numIterationsToStaggerCheck && g[0].c->math == c->math &&
+                   g[0].c->redblack == c->redblack && jacobi_reference_checks(g[0].c) == jacobi_reference_checks(c);
         };
         auto it = std::find_if(groups.begin(), groups.end(), same);
         if (it == groups.end()) groups.push_back({m});
@@ -189,8 +222,9 @@ std::vector<std::vector<Member>> group_fields(EpicHarmonicT *const *fields, unsi
                                     if (c->n == 3)   // (a forced F, capacity or shell depth batches from two fields: how the crossover is measured)
                                         return g.size() < (c->cfg.batch_fields || c->cfg.batch_brick_rows || c->cfg.batch_halo ? 2u : batch3d_from_fields(c->m)) ||
                                                batch_brick_plan(c->m, (unsigned)g.size(), c->cfg).capacity == 0;
-                                    return g.size() < (c->cfg.batch_fields ? 2u : batch_from_fields((long long)c->rows * c->cols)) ||
-                                           batch_plan(g[0].c->rows, g[0].c->cols, (unsigned)g.size(), g[0].c->cfg).fields == 0;
+                                    // (so does EPIC_HIP_BATCH=1 under EPIC_HIP_STUDY=1: the modes that are off by default)
+                                    return g.size() < (c->cfg.batch_fields || c->cfg.batch_forced ? 2u : batch_from_fields(c)) ||
+                                           batch_plan(c->rows, c->cols, (unsigned)g.size(), c->cfg, c->math, c->redblack).fields == 0;
                                 }),
                  groups.end());
     return groups;
@@ -231,10 +265,15 @@ struct Shared {
 // next check plus that check (iteration 0 is a check of its own), cut into launches of at most `halo` steps exactly like
 // enqueue_block in driver_loop.hip; the parity comes from the iteration number.  Three buffers per field rotate, as there: a block
 // never writes the buffer it started from, so whatever fails in it leaves every context in the state its last read check describes.
-// After a block the per-field maxima are read, converged fields are read back and leave, the table is repacked so that the workgroups
-// stay full, and the plan is made again for the fields that are left.  (The next block is NOT enqueued ahead of the check's read, as
-// the single-field loop does: DESIGN.md section 4.13.)  A group of 3-D fields runs the same loop on bricks: only the plan and the
-// launch differ (the third buffer of tiles_pipeline_ready is rows x pitch floats, and a 3-D context's rows are m[0] m[1]).
+// After a block the per-field maxima are read and every field's check is followed by what follows it in the single call
+// (Relaxation::after_check): a field that has ended -- or whose mode the check has changed: the tol mode's finishing phase, the Jacobi
+// hand-over -- leaves with the buffer, iteration number and delta of that check and goes through relax_to_end, which continues it as
+// harmonic_execute_gpu would (not at all, if it has ended) and reads it back; the table is repacked so that the workgroups stay full,
+// and the plan is made again for the fields that are left.  (The next block is NOT enqueued ahead of the check's read, as the
+// single-field loop does: DESIGN.md section 4.13.)  A Jacobi group under EPIC_HIP_JACOBI_CHECKS=reference runs its check as a launch
+// of its own, ONE red-black step of the same arithmetic, as enqueue_block does.  A group of 3-D fields runs the same loop on bricks:
+// only the plan and the launch differ (the third buffer of tiles_pipeline_ready is rows x pitch floats, and a 3-D context's rows are
+// m[0] m[1]).
 void run_group(std::vector<Member> &members, unsigned numThreads, int *rc, const char *fn)
 {
     const Config cfg = members[0].c->cfg;
@@ -242,6 +281,8 @@ void run_group(std::vector<Member> &members, unsigned numThreads, int *rc, const
     const unsigned stagger = members[0].h->numIterationsToStaggerCheck;
     const bool voxels = members[0].c->n == 3;
     const int m3[3] = {members[0].c->m[0], members[0].c->m[1], members[0].c->m[2]};
+    const int math = members[0].c->math;
+    const bool redblack = members[0].c->redblack, ref_checks = jacobi_reference_checks(members[0].c);
     std::vector<Member> live;
     for (const Member &m : members) {
         // an ordering point for every field, and the start of its relaxation (harmonic_execute_gpu)
@@ -266,6 +307,7 @@ void run_group(std::vector<Member> &members, unsigned numThreads, int *rc, const
         if (r != EPIC_SUCCESS) continue;
         m.h->delta = m.h->epsilon + 1.0f;
         live.push_back(m);
+        live.back().rx = std::make_shared<Relaxation>(m.h, m.c);
     }
     if (live.empty()) return;
     auto fail_all = [&](int code, const char *msg) {
@@ -282,7 +324,7 @@ void run_group(std::vector<Member> &members, unsigned numThreads, int *rc, const
     while (!live.empty()) {
         if (planned_for != live.size()) {   // (again whenever fields have retired)
             if (voxels) bplan = batch_brick_plan(m3, (unsigned)live.size(), cfg);
-            else plan = batch_plan(rows, cols, (unsigned)live.size(), cfg);
+            else plan = batch_plan(rows, cols, (unsigned)live.size(), cfg, math, redblack);
             planned_for = live.size();
         }
         const int F = voxels ? (bplan.capacity ? 1 : 0) : plan.fields;
@@ -305,13 +347,19 @@ void run_group(std::vector<Member> &members, unsigned numThreads, int *rc, const
         const unsigned total = first % stagger == 0 ? 1u : stagger - first % stagger + 1u;
         int src = 0;
         for (unsigned i = 0; i < total;) {
-            const unsigned k = std::min<unsigned>(total - i, (unsigned)halo);
+            unsigned k = std::min<unsigned>(total - i, (unsigned)halo);
+            if (ref_checks && i + k == total && k > 1) k--;   // (the reference's half-sweep: a launch of its own)
+            const bool half_sweep = redblack || (ref_checks && i + k == total);
             const int dst = src == 1 ? 2 : 1;
             const int parity = (int)((first + i) & 1u);
-            const hipError_t e = voxels ? epic_hip::launch_brick_3d_batch(sh.d_table, groups, src, dst, m3[0], m3[1], pitch, bplan.bp, bplan.capacity, (int)k,
-                                                                          parity, i + k == total, sh.stream)
-                                        : epic_hip::launch_tile_2d_batch(sh.d_table, groups, F, src, dst, rows, pitch, plan.tp, (int)k, parity, i + k == total,
-                                                                         sh.stream);
+            hipError_t e;
+            if (voxels)
+                e = epic_hip::launch_brick_3d_batch(sh.d_table, groups, src, dst, m3[0], m3[1], pitch, bplan.bp, bplan.capacity, (int)k, parity, i + k == total, sh.stream);
+            else if (math == 0 && half_sweep)
+                e = epic_hip::launch_tile_2d_batch(sh.d_table, groups, F, src, dst, rows, pitch, plan.tp, (int)k, parity, i + k == total, sh.stream);
+            else
+                e = epic_hip::launch_tile_2d_batch_modes(sh.d_table, groups, F, src, dst, rows, pitch, plan.tp, (int)k, math, half_sweep ? parity : -1,
+                                                         i + k == total, sh.stream);
             if (e != hipSuccess) {
                 (void)hipStreamSynchronize(sh.stream);
                 return fail_all(EPIC_ERROR_KERNEL_EXECUTION, "Failed to execute the batched 'Jacobi update' kernel.");
@@ -321,7 +369,7 @@ void run_group(std::vector<Member> &members, unsigned numThreads, int *rc, const
         }
         if (hipStreamSynchronize(sh.stream) != hipSuccess)
             return fail_all(EPIC_ERROR_DEVICE_SYNCHRONIZE, "Failed to synchronize the device after the batched 'update and check' kernel.");
-        // the check of every field; the converged ones leave
+        // the check of every field; the ones it ends, and the ones whose mode it changes, leave
         std::vector<Member> next;
         for (size_t s = 0; s < live.size(); s++) {
             const Member &m = live[s];
@@ -334,18 +382,14 @@ void run_group(std::vector<Member> &members, unsigned numThreads, int *rc, const
             m.h->delta = d;
             m.h->currentIteration = first + total;
             c->work_full += (double)total;
-            if (!(d < m.h->epsilon && m.h->currentIteration >= m.m_max)) {
+            m.rx->result = d < m.h->epsilon ? EPIC_SUCCESS_AND_CONVERGED : EPIC_SUCCESS;
+            m.rx->after_check();
+            if (!m.rx->over() && c->math == math && c->redblack == redblack) {
                 next.push_back(m);
                 continue;
             }
-            int r = harmonic_get_potential_values_gpu(m.h);
-            if (r != EPIC_SUCCESS) {
-                report(fn, "Failed to get all the potential values.");
-            } else {
-                r = harmonic_uninitialize_gpu(m.h);
-                if (r != EPIC_SUCCESS) report(fn, "Failed to uninitialize GPU variables.");
-            }
-            rc[m.index] = r;
+            rc[m.index] = relax_to_end(*m.rx, fn);
+            live[s].rx.reset();   // (the context has its mode back, as after the single call)
         }
         live.swap(next);
     }
@@ -452,7 +496,8 @@ int epic_hip_batch_plan(EpicHarmonicT *const *fields, unsigned int count, unsign
         const BrickBatchPlan b = batch_brick_plan(groups[0][0].c->m, (unsigned)groups[0].size(), groups[0][0].c->cfg);
         plan = BatchPlan{{b.bp.halo, b.bp.s0, b.bp.s1, 0, 0}, b.capacity ? 1 : 0};
     } else if (!groups.empty()) {
-        plan = batch_plan(groups[0][0].c->rows, groups[0][0].c->cols, (unsigned)groups[0].size(), groups[0][0].c->cfg);
+        const Ctx *c = groups[0][0].c;
+        plan = batch_plan(c->rows, c->cols, (unsigned)groups[0].size(), c->cfg, c->math, c->redblack);
     }
     if (batched) *batched = n;
     if (fields_per_workgroup) *fields_per_workgroup = plan.fields;

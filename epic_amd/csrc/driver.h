@@ -46,6 +46,7 @@
 #include <condition_variable>
 #include <functional>
 #include <map>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -334,6 +335,35 @@ bool due_tiles(Ctx *c, unsigned long long *due, unsigned long long *tiles, bool 
 int run_block(Harmonic *h, Ctx *c, unsigned plain, unsigned first, bool check, const char *fn, int bypass, bool run_ahead = false);
 // EPIC_HIP_JACOBI_CHECKS=reference on a context that runs the Jacobi scheme right now: its check iterations are the reference's half-sweeps (run_block)
 inline bool jacobi_reference_checks(const Ctx *c) { return c->cfg.jacobi_ref_checks && !c->redblack && c->n != 4; }
+// One relaxation of harmonic_execute_gpu between its start (currentIteration = 0, harmonic_initialize_gpu) and its end: what the loop
+// keeps from check to check -- the verdict of the latest check, the deltas the Jacobi hand-over and the tol mode's plateau warning look
+// back at, whether the finishing phase is on -- and the two rules that change a context's mode at a check (driver_loop.hip says why).
+// The batch driver (batch2d_driver.hip) runs the checks of a group's fields through after_check() and hands a field whose mode has
+// changed to relax_to_end(), which is harmonic_execute_gpu's own loop from that state on.  Going out of scope gives the context its
+// mode back, as the single call does when it returns.
+struct Relaxation {
+    Harmonic *h;
+    Ctx *c;
+    unsigned m_max = 0;            // max(m): no exit before this many iterations (harmonic_gpu.cu:266)
+    int result = EPIC_SUCCESS;     // of the latest iteration: EPIC_SUCCESS_AND_CONVERGED after a check with delta < epsilon
+    bool handed_over = false;      // Jacobi hand-over: the context runs the reference's half-sweeps from here on
+    float last_check = -1.0f;      // delta of the previous check (-1: none yet)
+    enum { kWindow = 32 };
+    float recent[kWindow];         // the deltas of the latest checks (a ring), for the plateau test of the tol mode's hand-over
+    int seen = 0;
+    int math0;
+    bool redblack0, finishing = false;   // tol: the finishing phase (precise, red-black) is on
+    bool finish_wanted = false;
+    float finish_below = 0.0f;
+    Relaxation(Harmonic *harmonic, Ctx *ctx);
+    Relaxation(const Relaxation &) = delete;
+    Relaxation &operator=(const Relaxation &) = delete;
+    ~Relaxation();
+    void after_check();            // what follows every check iteration (result and h->delta are the check's)
+    bool over() const { return result == EPIC_SUCCESS_AND_CONVERGED && h->currentIteration >= m_max; }
+};
+// harmonic_execute_gpu from the state r describes to its end: the loop, the read-back, harmonic_uninitialize_gpu; an EPIC_* code
+int relax_to_end(Relaxation &r, const char *fn);
 unsigned defer_cap(const Harmonic *h, const Ctx *c);   // deferred iterations that make a block worth enqueueing (1: no deferral)
 int flush_pending(Harmonic *h, Ctx *c, const char *fn);   // c may be null; an EPIC_* code (the failure of a deferred launch surfaces here)
 

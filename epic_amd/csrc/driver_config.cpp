@@ -109,6 +109,8 @@ Config Config::from_env()
         if (sscanf(e, "%dx%d", &s0, &s1) == 2 && s0 > 0 && s1 > 0) { c.brick_s0 = s0; c.brick_s1 = s1; }
     }
     c.batch = !is_zero("EPIC_HIP_BATCH");
+    e = env("EPIC_HIP_BATCH");
+    c.batch_forced = c.study && e && e[0] == '1';   // (as a study knob: every mode's groups from two fields on, batch2d_driver.hip)
     c.batch_fields = sint_of("EPIC_HIP_BATCH_FIELDS", 0);
     c.batch_halo = std::max(0, sint_of("EPIC_HIP_BATCH_HALO", 0));
     c.batch_rows = std::max(0, sint_of("EPIC_HIP_BATCH_ROWS", 0));

@@ -61,6 +61,7 @@ struct Config {
     int brick_halo = 0;              // EPIC_HIP_BRICK_HALO (0: the cost model)
     int brick_s0 = 0, brick_s1 = 0;  // EPIC_HIP_BRICK_DIMS=S0xS1: planes x rows of a brick, shells included (0: the cost model)
     bool batch = true;               // EPIC_HIP_BATCH=0: epic_hip_execute_batch_gpu / _complete_batch_gpu run every field through harmonic_execute_gpu (batch2d_driver.hip)
+    bool batch_forced = false;       // EPIC_HIP_BATCH=1 under EPIC_HIP_STUDY=1: groups of every batchable mode from two fields on, also where the batch is off by default
     int batch_fields = 0;            // EPIC_HIP_BATCH_FIELDS: fields per workgroup of the batched tile kernel, 1 | 2 | 4 (0: the cost model)
     int batch_halo = 0, batch_rows = 0, batch_width = 0;   // EPIC_HIP_BATCH_HALO / _ROWS / _WIDTH: its geometry, as the EPIC_HIP_TILE_* knobs (0: the cost model)
     int batch_brick_rows = 0;        // EPIC_HIP_BATCH_BRICK_ROWS=288|576: LDS capacity of the batched 3-D bricks (0: the cost model); their shell depth is EPIC_HIP_BATCH_HALO, their shape EPIC_HIP_BRICK_DIMS

@@ -301,10 +301,21 @@ int harmonic_execute_gpu(Harmonic *harmonic, unsigned int numThreads)  // harmon
         return result;
     }
 
-    unsigned int mMax = 0;
-    for (unsigned int i = 0; i < harmonic->n; i++) mMax = std::max(mMax, harmonic->m[i]);
     harmonic->delta = harmonic->epsilon + 1.0f;
+    Relaxation relaxation(harmonic, c);   // (the context outlives this function: it still holds the field and the mask)
+    return relax_to_end(relaxation, fn);
+}
 
+}  // extern "C"
+}  // namespace epic
+
+namespace epic_drv {
+
+using namespace epic;
+
+Relaxation::Relaxation(Harmonic *harmonic, Ctx *ctx) : h(harmonic), c(ctx), math0(ctx->math), redblack0(ctx->redblack)
+{
+    for (unsigned int i = 0; i < harmonic->n; i++) m_max = std::max(m_max, harmonic->m[i]);
     // The reference's loop (harmonic_gpu.cu:266-290): a sweep with currentIteration % stagger == 0 is a check
     // sweep; a plain sweep resets "converged"; exit right after a converged check with currentIteration >= mMax.
     // The plain sweeps between two checks need no host decision, so they are enqueued back to back.
@@ -318,18 +329,6 @@ int harmonic_execute_gpu(Harmonic *harmonic, unsigned int numThreads)  // harmon
     // in-place half-sweeps (what EPIC_HIP_SCHEME=redblack runs from the start), which end as the reference ends.  delta < 1
     // keeps the rule away from the phase in which the front still moves (delta ~1e6 for many checks in a row); a handover
     // that comes early costs time, never correctness.  oracle_jacobi_complete / oracle_tol_complete state the same rule.
-    struct Handover {
-        Ctx *c;
-        bool done = false;
-        float last_check = -1.0f;  // no check yet
-        // the deltas of the latest checks (a ring), for the plateau test of the tol mode's hand-over
-        enum { kWindow = 32 };
-        float recent[kWindow];
-        int seen = 0;
-        void note(float d) { recent[seen++ % kWindow] = d; }
-        float window_ago() const { return seen >= kWindow ? recent[seen % kWindow] : -1.0f; }   // the delta kWindow checks before the next one
-        ~Handover() { if (done) { c->redblack = false; force_all(c); } }
-    } handover{c};   // (the context outlives this function: it still holds the field and the mask)
     // Finish (tol math only; EPIC_HIP_TOL_FINISH=0 switches it off).  Where a converged f32 field ends inside the iteration's
     // dead band is decided by the last few per cent of the iterations, and the parity bar is on the reference's end point:
     // so at the first check with delta < 10 epsilon (100 epsilon when epsilon <= 1e-5: below) this loop leaves the tol arithmetic and continues with THE REFERENCE'S OWN
@@ -342,12 +341,6 @@ int harmonic_execute_gpu(Harmonic *harmonic, unsigned int numThreads)  // harmon
     // benchmark grid (45 001 + 9 800, where 82 % of the iterations run at the tol kernels' speed) -- and with them a tol Jacobi
     // relaxation is no faster to a converged field than the bit-exact default (round 3: 2.64 s against 2.51 s at 8192^2; tol
     // red-black: 2.20 s).  tol is a kernel-throughput mode; the time-to-solution numbers are in the bench line (relax*).
-    struct Finish {
-        Ctx *c;
-        int math0;
-        bool redblack0, on = false;
-        ~Finish() { if (on) { c->math = math0; c->redblack = redblack0; force_all(c); } }
-    } finish{c, c->math, c->redblack};
     // The switch only exists for relaxations to STAGNATION (epsilon <= 1e-5, where the tol iteration alone also comes to rest and
     // the finishing phase moves the end point by ~1e-5).  At the epsilons the reference's callers use (1e-3: the ROS plugin and
     // node; 1e-2: the python default) the loop stops while the field still moves, the iteration at which it stops decides the
@@ -360,7 +353,7 @@ int harmonic_execute_gpu(Harmonic *harmonic, unsigned int numThreads)  // harmon
         if (!said.exchange(true))
             fprintf(stderr, "Warning[epic_hip]: EPIC_HIP_TOL_FINISH=0 ignored for epsilon > 1e-5 (the relaxation stops before stagnation; the finishing iterations decide where).\n");
     }
-    const bool finish_wanted = c->math == 4 && !finish_off;
+    finish_wanted = c->math == 4 && !finish_off;
     // 10 at the epsilons the callers use (round 3's rule, verified there on every map of the reference), 100 for relaxations to
     // stagnation (epsilon <= 1e-5).  Round 4 swept the factor over all thirteen maps x {1e-2, 1e-3, 1e-6} x both schemes
     // (tools/finish_study_gpu.py): twelve maps are inside the bar for ANY factor; maps/trivial.png -- an almost
@@ -370,47 +363,63 @@ int harmonic_execute_gpu(Harmonic *harmonic, unsigned int numThreads)  // harmon
     // bit-exact default reproduces the reference there.
     float finish_factor = harmonic->epsilon <= kTolFinishOptionalBelow ? 100.0f : 10.0f;
     if (c->cfg.tol_finish_factor >= 1.0f) finish_factor = c->cfg.tol_finish_factor;   // EPIC_HIP_TOL_FINISH_FACTOR: study knob (tools/finish_study_gpu.py; include/epic_hip.h)
-    const float finish_below = finish_factor * harmonic->epsilon;
-    const unsigned stagger = harmonic->numIterationsToStaggerCheck;
-    result = EPIC_SUCCESS;
-    // what follows every check iteration (result and harmonic->delta are the check's)
-    auto after_check = [&] {
-        // (not at the FIRST check of a run that has not moved yet: a red-black iteration 0 whose colour has no cell next to a goal reports
-        //  delta = 0 exactly -- the 512^3 benchmark grid does --, and handing over there ran the whole relaxation in the reference's
-        //  arithmetic: correct, and not what the mode is for; round 6)
-        if (finish_wanted && !finish.on && harmonic->delta < finish_below && !(harmonic->delta == 0.0f && handover.seen == 0)) {
-            // A delta that has fallen by less than 0.3 % per check over the last 32 checks is a plateau on which the stop is decided
-            // by single ulps of single cells: maps/trivial.png falls 0.12-0.4 % per 100 iterations, in steps of one ulp of |u| < 8
-            // (at delta = 1e-5 = 21 ulp one step is 5 %, once in ~40 checks -- hence a window, not two successive checks).  There
-            // an arithmetic that is not the reference's bit for bit cannot promise the reference's stop, whatever the hand-over
-            // factor; the reference's other maps fall 0.8 % per check and faster.
-            const float ago = handover.window_ago();
-            if (ago > 0.0f && harmonic->delta > 0.908f * ago)   // 0.997^32
-                fprintf(stderr, "Warning[epic_hip]: tol math on a slowly converging map (delta %.3e, %.3e %d checks earlier): the stop is decided by "
-                                "single ulps here and the tol arithmetic cannot promise the 1e-5 parity bar; the default (precise) math reproduces the reference.\n",
-                        (double)harmonic->delta, (double)ago, (int)Handover::kWindow);
-            finish.on = true;
-            c->finish_from = harmonic->currentIteration;
-            c->math = 0;          // precise
-            c->redblack = true;   // the reference's half-sweeps, colour by currentIteration
-            force_all(c);
-            // Relaxations to stagnation (epsilon <= 1e-5): only a check of the finishing phase may end the loop -- there the finishing
-            // iterations decide the end point.  At the callers' epsilons THIS check keeps its verdict (round 6; found by the campaign of
-            // tests/tol_campaign.py on maps that converge within a few checks: delta falls from above 10 epsilon to below epsilon between
-            // two checks, the reference stops here, and 100 more iterations at an epsilon at which the field still moves ended up to
-            // 7e-4 away).  The tol delta of an iteration is the reference's to an ulp or two of |u|: as good a judge of "below epsilon"
-            // as a finishing phase's delta would be 100 iterations later.  oracle_tol_complete and SlabSolver.solve state the same rule.
-            if (!(harmonic->epsilon > kTolFinishOptionalBelow)) result = EPIC_SUCCESS;
-        } else if (!c->redblack && result == EPIC_SUCCESS && harmonic->delta < 1.0f && handover.last_check >= 0.0f &&
-                   harmonic->delta >= handover.last_check) {
-            c->redblack = true;
-            force_all(c);
-            handover.done = true;
-        }
-        handover.last_check = harmonic->delta;
-        handover.note(harmonic->delta);
-    };
-    while (result != EPIC_SUCCESS_AND_CONVERGED || harmonic->currentIteration < mMax) {
+    finish_below = finish_factor * harmonic->epsilon;
+}
+
+Relaxation::~Relaxation()
+{
+    if (finishing) { c->math = math0; c->redblack = redblack0; force_all(c); }
+    if (handed_over) { c->redblack = false; force_all(c); }
+}
+
+// what follows every check iteration (result and h->delta are the check's)
+void Relaxation::after_check()
+{
+    Harmonic *const harmonic = h;
+    // (not at the FIRST check of a run that has not moved yet: a red-black iteration 0 whose colour has no cell next to a goal reports
+    //  delta = 0 exactly -- the 512^3 benchmark grid does --, and handing over there ran the whole relaxation in the reference's
+    //  arithmetic: correct, and not what the mode is for; round 6)
+    if (finish_wanted && !finishing && harmonic->delta < finish_below && !(harmonic->delta == 0.0f && seen == 0)) {
+        // A delta that has fallen by less than 0.3 % per check over the last 32 checks is a plateau on which the stop is decided
+        // by single ulps of single cells: maps/trivial.png falls 0.12-0.4 % per 100 iterations, in steps of one ulp of |u| < 8
+        // (at delta = 1e-5 = 21 ulp one step is 5 %, once in ~40 checks -- hence a window, not two successive checks).  There
+        // an arithmetic that is not the reference's bit for bit cannot promise the reference's stop, whatever the hand-over
+        // factor; the reference's other maps fall 0.8 % per check and faster.
+        const float ago = seen >= kWindow ? recent[seen % kWindow] : -1.0f;   // the delta kWindow checks before this one
+        if (ago > 0.0f && harmonic->delta > 0.908f * ago)   // 0.997^32
+            fprintf(stderr, "Warning[epic_hip]: tol math on a slowly converging map (delta %.3e, %.3e %d checks earlier): the stop is decided by "
+                            "single ulps here and the tol arithmetic cannot promise the 1e-5 parity bar; the default (precise) math reproduces the reference.\n",
+                    (double)harmonic->delta, (double)ago, (int)kWindow);
+        finishing = true;
+        c->finish_from = harmonic->currentIteration;
+        c->math = 0;          // precise
+        c->redblack = true;   // the reference's half-sweeps, colour by currentIteration
+        force_all(c);
+        // Relaxations to stagnation (epsilon <= 1e-5): only a check of the finishing phase may end the loop -- there the finishing
+        // iterations decide the end point.  At the callers' epsilons THIS check keeps its verdict (round 6; found by the campaign of
+        // tests/tol_campaign.py on maps that converge within a few checks: delta falls from above 10 epsilon to below epsilon between
+        // two checks, the reference stops here, and 100 more iterations at an epsilon at which the field still moves ended up to
+        // 7e-4 away).  The tol delta of an iteration is the reference's to an ulp or two of |u|: as good a judge of "below epsilon"
+        // as a finishing phase's delta would be 100 iterations later.  oracle_tol_complete and SlabSolver.solve state the same rule.
+        if (!(harmonic->epsilon > kTolFinishOptionalBelow)) result = EPIC_SUCCESS;
+    } else if (!c->redblack && result == EPIC_SUCCESS && harmonic->delta < 1.0f && last_check >= 0.0f &&
+               harmonic->delta >= last_check) {
+        c->redblack = true;
+        force_all(c);
+        handed_over = true;
+    }
+    last_check = harmonic->delta;
+    recent[seen++ % kWindow] = harmonic->delta;
+}
+
+int relax_to_end(Relaxation &r, const char *fn)
+{
+    Harmonic *const harmonic = r.h;
+    Ctx *const c = r.c;
+    int &result = r.result;
+    const unsigned mMax = r.m_max, stagger = harmonic->numIterationsToStaggerCheck;
+    auto after_check = [&] { r.after_check(); };
+    while (!r.over()) {
         if (harmonic->currentIteration % stagger == 0) {
             result = update_and_check(harmonic, false);
             if (result != EPIC_SUCCESS && result != EPIC_SUCCESS_AND_CONVERGED) {
@@ -548,6 +557,11 @@ int harmonic_execute_gpu(Harmonic *harmonic, unsigned int numThreads)  // harmon
     }
     return EPIC_SUCCESS;
 }
+
+}  // namespace epic_drv
+
+namespace epic {
+extern "C" {
 
 int harmonic_complete_gpu(Harmonic *harmonic, unsigned int numThreads)  // harmonic_gpu.cu:168-201
 {

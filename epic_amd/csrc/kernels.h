@@ -200,6 +200,12 @@ int tile_2d_batch_max_fields(int width);   // fields one workgroup holds of the 
 // fields' tile_delta.  fields_per_group: 1, 2 or 4, at most tile_2d_batch_max_fields(plan's width).
 hipError_t launch_tile_2d_batch(const BatchField *d_fields, int groups, int fields_per_group, int src, int dst, int rows, int pitch,
                                 const TilePlan &plan, int steps, int parity, bool check, hipStream_t stream);
+// The same for the other modes (kernels_tile2d_batch_modes.hip): math = tol (either scheme), fast (either scheme) or precise with
+// parity < 0 (Jacobi); parity as launch_tile_2d has it.  Fields one workgroup holds of a tile of that arithmetic, scheme and width; 0:
+// no such instantiation (precise red-black among them: that is launch_tile_2d_batch).
+int tile_2d_batch_modes_max_fields(int math, bool redblack, int width);
+hipError_t launch_tile_2d_batch_modes(const BatchField *d_fields, int groups, int fields_per_group, int src, int dst, int rows, int pitch,
+                                      const TilePlan &plan, int steps, int math, int parity, bool check, hipStream_t stream);
 
 // ---- streamlines on the resident field (path_2d.hip): one lane per start point ----------------
 // d_pts: n_paths x 2 * max_points floats; d_k: points per path (0 on failure); d_rc: EPIC_* code per path.

@@ -438,20 +438,24 @@ int epic_hip_config_reload(EpicHarmonicT *harmonic);
  * numThreads % 32 != 0: EPIC_ERROR_INVALID_CUDA_PARAM; nothing runs then.  A field that fails harmonic_execute_gpu's own validation
  * (a null member, epsilon <= 0, stagger 0, no device state, n = 4) gets its code in results[i]; the other fields run.  A device error
  * inside a batched block gives every field still in the batch that code and leaves its context in the state its last check describes.
- * WHERE the iterations run: fields with n == 2 that share m and numIterationsToStaggerCheck, whose contexts are in the library's
- * default mode (precise math, red-black scheme, one device) on a grid the LDS tiles serve (epic_hip_tile_iterations > 0), advance
- * TOGETHER -- one launch for all of them, a workgroup holding the same tile of up to four fields (epic_amd/csrc/kernels_tile2d_batch.hip);
- * epsilon may differ per field.  Fields with n == 3 are batched the same way: those that share all three extents and
+ * WHERE the iterations run: fields with n == 2 that share m, numIterationsToStaggerCheck and a mode -- arithmetic, scheme,
+ * EPIC_HIP_JACOBI_CHECKS -- on one device and a grid the LDS tiles serve (epic_hip_tile_iterations > 0) advance TOGETHER, one launch
+ * for all of them, a workgroup holding the same tile of up to four fields: the library's default mode (precise, red-black) through
+ * epic_amd/csrc/kernels_tile2d_batch.hip, tol (either scheme), precise Jacobi and fast through kernels_tile2d_batch_modes.hip; epsilon
+ * may differ per field.  A field whose check starts the tol mode's finishing phase or the Jacobi hand-over leaves its group at that
+ * check and finishes alone, exactly as harmonic_execute_gpu finishes it (epic_hip_finish_iteration reports the same iteration).  Fields with n == 3 are batched the same way: those that share all three extents and
  * numIterationsToStaggerCheck, in the default mode on a grid the LDS bricks serve (epic_hip_brick_iterations > 0), advance together on
  * bricks, one field per workgroup (epic_amd/csrc/kernels_brick3d_batch.hip) -- where that was measured faster than the loop: from four
  * fields between 32^3 and 64^3 cells and above 64 x 64 x 200 up to 96^3, from two in between, never below 32^3 or above 96^3; a lone
  * 3-D field is never batched.  Every other field
- * (tol or fast math, Jacobi, a shape of its own, fewer 2-D fields of a shape than the measured crossover: two up to 0.25 Mcell, four
- * above) runs through harmonic_execute_gpu inside the same call.  Both calls are ordering points for every field.  EPIC_HIP_BATCH=0:
- * every field through harmonic_execute_gpu.
+ * (a shape or a mode of its own, fast math, fewer 2-D fields of a shape and mode than the measured crossover -- default mode: two up to
+ * 0.25 Mcell, four above; tol and precise Jacobi: four, tol Jacobi above 0.25 Mcell sixteen; fast: never, it was not measured)
+ * runs through harmonic_execute_gpu inside the same call.  Both calls are ordering points for every field.  EPIC_HIP_BATCH=0:
+ * every field through harmonic_execute_gpu; EPIC_HIP_BATCH=1 (a study knob: with EPIC_HIP_STUDY=1) batches every mode from two fields.
  * Study knobs: EPIC_HIP_BATCH_FIELDS (fields per workgroup: 1, 2, 4), EPIC_HIP_BATCH_HALO / _ROWS / _WIDTH (the tiles' geometry); 3-D:
  * EPIC_HIP_BATCH_HALO (shell depth), EPIC_HIP_BRICK_DIMS (S0xS1 of a brick), EPIC_HIP_BATCH_BRICK_ROWS = 288 | 576 (LDS capacity).
- * Measured against a loop of harmonic_complete_gpu: DESIGN.md sections 4.13 and 4.14, profiles/batch_2d.txt, profiles/batch_3d.txt. */
+ * Measured against a loop of harmonic_complete_gpu: DESIGN.md sections 4.13, 4.13b and 4.14, profiles/batch_2d.txt,
+ * profiles/batch_2d_modes.txt, profiles/batch_3d.txt. */
 int epic_hip_execute_batch_gpu(EpicHarmonicT *const *fields, unsigned int count, unsigned int numThreads, int *results);
 int epic_hip_complete_batch_gpu(EpicHarmonicT *const *fields, unsigned int count, unsigned int numThreads, int *results);
 /* What the two calls above would do with these fields now: *batched = how many go through the batched kernel (0: none), and the

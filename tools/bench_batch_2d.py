@@ -7,7 +7,9 @@ same with the fields per workgroup forced to 1, 2 and 4 (EPIC_HIP_BATCH_FIELDS),
 and with the tile width forced to 64 and 128 columns (EPIC_HIP_BATCH_WIDTH), fields per workgroup 1, for the wide tile's.
 
     python tools/bench_batch_2d.py [--maps basic,maze,umass] [--fields 1,2,4,8,16,32,64] [--eps 1e-3,1e-6] [--forced 1,2,4] [--forced-width 64,128] [--forced-fields 2,8,32]
-profiles/batch_2d.txt is this tool's output.
+                                   [--math precise|tol|fast] [--scheme redblack|jacobi]
+profiles/batch_2d.txt is this tool's output; profiles/batch_2d_modes.txt its output with --math / --scheme, where the batch is forced
+(EPIC_HIP_BATCH=1: those modes' groups are off by default) and the loop is harmonic_complete_gpu in the same mode.
 """
 import argparse
 import os
@@ -30,6 +32,8 @@ def main():
     ap.add_argument("--forced-width", default="64,128", help="tile widths of the forced-plan rows (one field per workgroup)")
     ap.add_argument("--forced-fields", default="2,8,32", help="B of the forced-plan rows")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--math", default="precise")
+    ap.add_argument("--scheme", default="redblack")
     args = ap.parse_args()
     from epic_amd import epic_harmonic as eh
     from epic_amd.harmonic import Harmonic
@@ -38,6 +42,9 @@ def main():
     E = eh._epic
     for knob in ("EPIC_HIP_SCHEME", "EPIC_HIP_MATH", "EPIC_HIP_BATCH_FIELDS", "EPIC_HIP_BATCH_WIDTH"):
         os.environ.pop(knob, None)
+    if (args.math, args.scheme) != ("precise", "redblack"):
+        os.environ.update(EPIC_HIP_MATH=args.math, EPIC_HIP_SCHEME=args.scheme, EPIC_HIP_BATCH="1")
+        print("# math %s, scheme %s, batch forced" % (args.math, args.scheme))
 
     def stat(v):
         return "%9.4f (+%4.1f %%)" % (min(v), 100.0 * (max(v) - min(v)) / min(v))
@@ -99,7 +106,7 @@ def main():
         free = np.flatnonzero(base.locked_array().ravel() == 0)
         goals = np.random.default_rng(20240601).choice(free, size=64, replace=False)
         for eps in [float(e) for e in args.eps.split(",")]:
-            for b in [int(x) for x in args.fields.split(",")]:
+            for b in [int(x) for x in args.fields.split(",") if x]:
                 row(name, base, goals[:b], eps, 0)
             for b in [int(x) for x in args.forced_fields.split(",") if x]:
                 for f in [int(x) for x in args.forced.split(",") if x]:
