@@ -374,6 +374,7 @@ hipError_t launch_occupancy_region(float *u, uint32_t *maskw, const unsigned cha
 // The plan is made on the host; d_scratch: 8-byte aligned device memory of plan.scratch_bytes() (the source bits, then the table).
 // upload_occupancy_inflate copies the table there (the plan must live until the stream has run the copy), launch_occupancy_inflate
 // enqueues the two kernels behind it.  Called from occupancy_driver.hip only.
+// bits_ready: the source bits at d_scratch are the caller's (the hit plane of occupancy_points.hip); only the dilation kernel runs.
 struct OccInflatePlan {
     int extent[3];
     unsigned radius_sq;
@@ -386,7 +387,19 @@ struct OccInflatePlan {
 OccInflatePlan plan_occupancy_inflate(const int extent[3], unsigned radius_sq);
 hipError_t upload_occupancy_inflate(const OccInflatePlan &plan, void *d_scratch, hipStream_t stream);
 hipError_t launch_occupancy_inflate(const OccInflatePlan &plan, unsigned char *d_occ, void *d_scratch, int obstacle_threshold, int no_change,
-                                    unsigned flags, hipStream_t stream);
+                                    unsigned flags, hipStream_t stream, bool bits_ready = false);
+
+// ---- points to a block of bytes (occupancy_points.hip) ---------------------------------------------------------------------
+// n_points points of n floats at d_points (device, 8-byte aligned) and the sensor (host, n floats, may be null: no ray clearing)
+// become the block B of epic_hip_set_occupancy_points_* at d_occ: extent[0] * extent[1] rows of extent[2] bytes, every byte written.
+// d_hit / d_clear: the two bit planes, extent[0] * extent[1] * occupancy_points_nwords(extent) words each, ZEROED by the caller; after
+// the launch d_hit holds the source bits of B in the layout launch_occupancy_inflate reads (bits_ready).  origin / extent: the box in
+// the order of m, tested by the caller (pts::args_ok; a sensor lies inside it).  Called from occupancy_driver.hip only.
+constexpr unsigned long long kOccPointsMaxWords = 0x3fffffffull;   // words of a plane: four lanes per word fit 32 bits
+inline unsigned occupancy_points_nwords(const int extent[3]) { return ((unsigned)extent[2] + 63u) / 64u; }
+hipError_t launch_occupancy_points(const float *d_points, unsigned n_points, unsigned n, const float *sensor, const int origin[3],
+                                   const int extent[3], unsigned long long *d_hit, unsigned long long *d_clear, unsigned char *d_occ,
+                                   int no_change, unsigned flags, hipStream_t stream);
 
 // ---- queries of the resident field (field_query.hip); called from field_query_driver.hip only ------------------------------
 // The field as the context holds it; a 2-D field is one plane: m0 = 1, m1 = rows.  Nothing is written to u or the masks.

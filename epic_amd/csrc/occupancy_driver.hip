@@ -22,9 +22,13 @@
 // bytes and the region kernel the launchers of occupancy_inflate.hip edit the uploaded bytes in place, with their scratch (source bits,
 // offset table) behind the bytes in the same temporary.  kernel_ms then times that step.  On slabs a 2-D block is inflated on the host
 // (occupancy_rule.h: occupancy_inflate_block) and takes the list route; a 3-D field names the host route as above.
+//
+// The points form (epic_hip_set_occupancy_points_gpu) is the inflated form whose bytes never exist on the host: the launcher of
+// occupancy_points.hip writes them on the device from the uploaded points (set_occupancy_points below).
 #include <functional>
 
 #include "driver.h"
+#include "occupancy_points_rule.h"
 #include "occupancy_rule.h"
 
 namespace epic_drv {
@@ -108,10 +112,11 @@ int multi_dense_edit(Harmonic *h, Ctx *c, const unsigned char *occ, int obstacle
 // prepare (the inflated form; empty otherwise): a launch that edits the bytes on the device before `launch` reads them, with `extra`
 // bytes of scratch behind them (16-byte aligned).  Called twice: kernels == false for its uploads, then kernels == true between the
 // events, which then bracket prepare's kernels, not launch
+// upload == false (the points form): nothing is copied to d_occ; prepare's kernels write every byte of it
 using Prepare = std::function<hipError_t(unsigned char *d_occ, void *d_scratch, bool kernels)>;
 template <class Launch>
 int staged_edit(Ctx *c, const void *occ, size_t bytes, unsigned flags, unsigned long long *changed, float *kernel_ms, const char *fn, Launch launch,
-                size_t extra = 0, const Prepare &prepare = Prepare())
+                size_t extra = 0, const Prepare &prepare = Prepare(), bool upload = true)
 {
     const size_t scratch_at = (bytes + 15) & ~(size_t)15;
     const size_t slot = epic_hip::kOccCounterBytes;
@@ -133,7 +138,7 @@ int staged_edit(Ctx *c, const void *occ, size_t bytes, unsigned flags, unsigned 
         unsigned long long *d_changed = reinterpret_cast<unsigned long long *>(tmp);
         unsigned char *d_occ = tmp + slot;
         if (hipMemsetAsync(d_changed, 0, slot, c->stream) != hipSuccess ||
-            hipMemcpyAsync(d_occ, occ, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+            (upload && hipMemcpyAsync(d_occ, occ, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)) {
             report(fn, "Failed to copy memory from host to device for the occupancy image.");
             rc = EPIC_ERROR_MEMCPY_TO_DEVICE;
         } else if ((prepare && prepare(d_occ, d_occ + scratch_at, false) != hipSuccess) ||
@@ -253,6 +258,79 @@ int set_occupancy_region(Harmonic *harmonic, const void *occ, const unsigned *or
                        });
 }
 
+// The points form, n in {2, 3}: the inflated form without its upload.  The block is written on the device by the launcher of
+// occupancy_points.hip from the points, which are all that crosses the bus; its hit plane stands where the inflation expects its
+// source bits.  The temporary behind the block: hit plane | offset table (radius_sq != 0) | clear plane | points, each on a 16-byte
+// boundary; the planes are zeroed before the events, kernel_ms covers the points kernels and the dilation.
+// On slabs the host builds B (occupancy_points_rule.h) and the call goes on as the inflated form.
+int set_occupancy_points(Harmonic *harmonic, unsigned n_points, const float *points, const float *sensor, const unsigned *origin,
+                         const unsigned *extent, int obstacle_threshold, int no_change, unsigned flags, unsigned radius_sq,
+                         unsigned long long *changed, float *kernel_ms, const char *fn)
+{
+    size_t m[3], o[3], e[3];
+    epic_hip::pts::Box box;
+    const bool host_ok = radius_sq <= EPIC_HIP_OCC_MAX_RADIUS_SQ && harmonic != nullptr && harmonic->m != nullptr && harmonic->u != nullptr &&
+                         harmonic->locked != nullptr && epic_hip::occupancy_region(harmonic->n, harmonic->m, origin, extent, m, o, e) &&
+                         epic_hip::pts::args_ok(harmonic->n, o, e, n_points, points, sensor, obstacle_threshold, no_change, flags, box);
+    Ctx *c = host_ok ? find_ctx(harmonic) : nullptr;
+    if (c == nullptr || !ready(harmonic, c) || c->n != (int)harmonic->n || !same_dims(harmonic, c)) {
+        report(fn, "Invalid data.");
+        return EPIC_ERROR_INVALID_DATA;
+    }
+    const unsigned n = harmonic->n;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (c->multi()) {
+        std::vector<unsigned char> block(e[0] * e[1] * e[2]);
+        epic_hip::pts::rasterize(box, n, n_points, points, sensor, no_change, flags, block.data());
+        return set_occupancy_region(harmonic, block.data(), origin, extent, obstacle_threshold, no_change, flags, changed, nullptr, fn, radius_sq);
+    }
+    const size_t plane_bytes = e[0] * e[1] * (size_t)epic_hip::occupancy_points_nwords(box.e) * sizeof(unsigned long long);
+    if (plane_bytes / sizeof(unsigned long long) > epic_hip::kOccPointsMaxWords) {
+        report(fn, "Invalid data.");
+        return EPIC_ERROR_INVALID_DATA;
+    }
+    {
+        const int frc = flush_pending(harmonic, c, fn);   // the iterations counted so far act on the cells as they were
+        if (frc != EPIC_SUCCESS) return frc;
+    }
+
+    epic_hip::OccRegion region;
+    region.m0 = (int)m[0];
+    region.m1 = (int)m[1];
+    region.cols = (int)m[2];
+    for (int a = 0; a < 3; a++) {
+        region.origin[a] = box.o[a];
+        region.extent[a] = box.e[a];
+    }
+    region.faces0 = c->n == 3;
+    const auto ingest = [&](const unsigned char *d_occ, unsigned long long *d_changed) {
+        return epic_hip::launch_occupancy_region(c->buf[c->cur], c->maskw, d_occ, region, c->pitch, obstacle_threshold, no_change, flags, d_changed,
+                                                 c->stream);
+    };
+    epic_hip::OccInflatePlan plan;   // lives until staged_edit has synchronised
+    if (radius_sq) plan = epic_hip::plan_occupancy_inflate(region.extent, radius_sq);
+    const auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t clear_at = align16(plane_bytes + plan.table.size() * sizeof(int)), points_at = align16(clear_at + plane_bytes);
+    const size_t points_bytes = (size_t)n_points * n * sizeof(float);
+    return staged_edit(
+        c, nullptr, e[0] * e[1] * e[2], flags, changed, kernel_ms, fn, ingest, points_at + points_bytes,
+        [&](unsigned char *d_occ, void *d_scratch, bool kernels) {
+            unsigned char *s = static_cast<unsigned char *>(d_scratch);
+            if (!kernels) {
+                hipError_t err = hipMemsetAsync(s, 0, clear_at + plane_bytes, c->stream);
+                if (err == hipSuccess && radius_sq) err = epic_hip::upload_occupancy_inflate(plan, d_scratch, c->stream);
+                if (err == hipSuccess && points_bytes) err = hipMemcpyAsync(s + points_at, points, points_bytes, hipMemcpyHostToDevice, c->stream);
+                return err;
+            }
+            const hipError_t err = epic_hip::launch_occupancy_points(reinterpret_cast<const float *>(s + points_at), n_points, n, sensor, box.o, box.e,
+                                                                     reinterpret_cast<unsigned long long *>(s),
+                                                                     reinterpret_cast<unsigned long long *>(s + clear_at), d_occ, no_change, flags, c->stream);
+            if (err != hipSuccess || radius_sq == 0) return err;
+            return epic_hip::launch_occupancy_inflate(plan, d_occ, d_scratch, obstacle_threshold, no_change, flags, c->stream, true);
+        },
+        false);
+}
+
 }  // namespace
 
 }  // namespace epic_drv
@@ -333,6 +411,14 @@ int epic_hip_set_occupancy_inflated_gpu(Harmonic *harmonic, const void *occ, con
                                         kernel_ms && radius_sq ? &ms : nullptr, fn, radius_sq);
     if (rc == EPIC_SUCCESS && kernel_ms) *kernel_ms = ms;
     return rc;
+}
+
+int epic_hip_set_occupancy_points_gpu(Harmonic *harmonic, unsigned int n_points, const float *points, const float *sensor,
+                                      const unsigned int *origin, const unsigned int *extent, int obstacle_threshold, int no_change,
+                                      unsigned flags, unsigned int radius_sq, unsigned long long *changed, float *kernel_ms)
+{
+    return set_occupancy_points(harmonic, n_points, points, sensor, origin, extent, obstacle_threshold, no_change, flags, radius_sq, changed,
+                                kernel_ms, "epic_hip_set_occupancy_points_gpu");
 }
 
 // unlocked cells are interior cells (the faces and the padding are locked in the masks), and the 3-D masks are the 2-D lane masks

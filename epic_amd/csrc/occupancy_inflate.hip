@@ -190,7 +190,7 @@ hipError_t upload_occupancy_inflate(const OccInflatePlan &p, void *d_scratch, hi
 }
 
 hipError_t launch_occupancy_inflate(const OccInflatePlan &p, unsigned char *d_occ, void *d_scratch, int obstacle_threshold, int no_change,
-                                    unsigned flags, hipStream_t stream)
+                                    unsigned flags, hipStream_t stream, bool bits_ready)
 {
     if (!d_occ || !d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) % 8) != 0 || p.table.empty() || p.radius_sq > 256u) return hipErrorInvalidValue;
     for (int a = 0; a < 3; a++)
@@ -220,12 +220,14 @@ hipError_t launch_occupancy_inflate(const OccInflatePlan &p, unsigned char *d_oc
     const dim3 grid1((unsigned)((pairs + kWavesPerBlock - 1) / kWavesPerBlock)), block1(kWave * kWavesPerBlock);
     const dim3 grid2((unsigned)bricks), block2((unsigned)(p.tz * p.ty * kBrickWords));   // one lane per output word: 64 or 256
     if (dword) {
-        hipLaunchKernelGGL(occupancy_source_bits_kernel<true>, grid1, block1, 0, stream, d_occ, d_bits, p.extent[2], (unsigned)p.nwords,
-                           (unsigned)pairs, obstacle_threshold, no_change, flags);
+        if (!bits_ready)
+            hipLaunchKernelGGL(occupancy_source_bits_kernel<true>, grid1, block1, 0, stream, d_occ, d_bits, p.extent[2], (unsigned)p.nwords,
+                               (unsigned)pairs, obstacle_threshold, no_change, flags);
         hipLaunchKernelGGL(occupancy_inflate_kernel<true>, grid2, block2, lds_bytes, stream, d_occ, d_bits, d_table, g);
     } else {
-        hipLaunchKernelGGL(occupancy_source_bits_kernel<false>, grid1, block1, 0, stream, d_occ, d_bits, p.extent[2], (unsigned)p.nwords,
-                           (unsigned)pairs, obstacle_threshold, no_change, flags);
+        if (!bits_ready)
+            hipLaunchKernelGGL(occupancy_source_bits_kernel<false>, grid1, block1, 0, stream, d_occ, d_bits, p.extent[2], (unsigned)p.nwords,
+                               (unsigned)pairs, obstacle_threshold, no_change, flags);
         hipLaunchKernelGGL(occupancy_inflate_kernel<false>, grid2, block2, lds_bytes, stream, d_occ, d_bits, d_table, g);
     }
     return hipGetLastError();

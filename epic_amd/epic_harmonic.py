@@ -162,6 +162,11 @@ _SIGNATURES = {
     "epic_hip_set_occupancy_inflated_cpu": (_H, ct.c_void_p, _UP, _UP, ct.c_int, ct.c_int, ct.c_uint, ct.c_uint, ct.POINTER(ct.c_ulonglong)),
     "epic_hip_set_occupancy_inflated_gpu": (_H, ct.c_void_p, _UP, _UP, ct.c_int, ct.c_int, ct.c_uint, ct.c_uint, ct.POINTER(ct.c_ulonglong),
                                             ct.POINTER(ct.c_float)),
+    # the inflated calls on a block built from n_points points of n floats, (x, y[, z]), and a sensor (may be None: no ray clearing)
+    "epic_hip_set_occupancy_points_cpu": (_H, ct.c_uint, ct.c_void_p, ct.c_void_p, _UP, _UP, ct.c_int, ct.c_int, ct.c_uint, ct.c_uint,
+                                          ct.POINTER(ct.c_ulonglong)),
+    "epic_hip_set_occupancy_points_gpu": (_H, ct.c_uint, ct.c_void_p, ct.c_void_p, _UP, _UP, ct.c_int, ct.c_int, ct.c_uint, ct.c_uint,
+                                          ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_float)),
     "epic_hip_reset_free_cells_3d_cpu": (_H,),
     "epic_hip_reset_free_cells_3d_gpu": (_H,),
     # field queries: points are n floats each, cell lists n unsigned each, origin / extent n entries in the order of m

@@ -161,6 +161,44 @@ class Harmonic(eh.EpicHarmonic):
                     raise RuntimeError("epic_amd: %s failed with code %d" % (variant.__name__, rc))
         return int(changed.value)
 
+    def set_points(self, points, sensor=None, origin=None, extent=None, inflate_sq=0, obstacle_threshold=50, no_change=-2, keep_free=False,
+                   unsigned=False, over_goals=False, process='gpu'):
+        """Apply a point cloud or a laser scan (epic_hip_set_occupancy_points_*, include/epic_hip.h): ``points`` is k x n float32 in
+        cell units, (x, y[, z]) with x along the last axis of m -- the array ``epic_hip_sample_potential_*`` takes.  The cell of
+        every point inside the box ``origin`` / ``extent`` (n entries each in the order of m; both None: the grid) becomes an
+        obstacle, grown by sqrt(``inflate_sq``) cells; with a ``sensor`` (n floats, inside the box) the cells its beams cross on
+        the way become free; every other cell is left alone.  The other keywords are those of ``set_occupancy``; ``no_change``
+        must be a value of the byte type.  On the device only the points cross the bus.  Returns ``changed``."""
+        if process not in ('gpu', 'cpu', 'both'):
+            raise ValueError("process must be 'gpu', 'cpu' or 'both'")
+        n = int(self.n)
+        points = np.ascontiguousarray(np.asarray(points, dtype=np.float32))
+        if n not in (2, 3) or points.size % n != 0:
+            raise ValueError("points must hold n = %d floats each, on a 2-D or 3-D grid" % n)
+        if sensor is not None:
+            sensor = np.ascontiguousarray(np.asarray(sensor, dtype=np.float32)).reshape(-1)
+            if sensor.size != n:
+                raise ValueError("the sensor has n = %d coordinates" % n)
+        if (origin is None) != (extent is None):
+            raise ValueError("origin and extent come together")
+        UP = ct.POINTER(ct.c_uint)
+        where = (None, None)
+        if origin is not None:
+            origin, extent = (np.ascontiguousarray(np.asarray(v, dtype=np.uint32)).reshape(-1) for v in (origin, extent))
+            where = (origin.ctypes.data_as(UP), extent.ctypes.data_as(UP))
+        flags = ((eh.EPIC_HIP_OCC_KEEP_FREE if keep_free else 0) | (eh.EPIC_HIP_OCC_UNSIGNED if unsigned else 0)
+                 | (eh.EPIC_HIP_OCC_OVER_GOALS if over_goals else 0))
+        changed = ct.c_ulonglong(0)
+        args = (self, points.size // n, points.ctypes.data if points.size else None, sensor.ctypes.data if sensor is not None else None, *where,
+                int(obstacle_threshold), int(no_change), flags, int(inflate_sq), ct.byref(changed))
+        for variant, tail, wanted in ((eh._epic.epic_hip_set_occupancy_points_cpu, (), ('cpu', 'both')),
+                                      (eh._epic.epic_hip_set_occupancy_points_gpu, (None,), ('gpu', 'both'))):
+            if process in wanted:
+                rc = variant(*args, *tail)
+                if rc != 0:
+                    raise RuntimeError("epic_amd: %s failed with code %d" % (variant.__name__, rc))
+        return int(changed.value)
+
     def reset_free_cells(self, process='gpu'):
         """Every unlocked interior cell back to EPIC_LOG_SPACE_FREE (the node's reset_free_cells service), on a 2-D or a 3-D
         grid; ``process`` as in ``set_occupancy``."""

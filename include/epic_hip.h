@@ -298,6 +298,39 @@ int epic_hip_set_occupancy_inflated_gpu(EpicHarmonicT *h, const void *occ, const
                                         int obstacle_threshold, int no_change, unsigned flags, unsigned int radius_sq,
                                         unsigned long long *changed, float *kernel_ms /* may be NULL */);
 
+/* ---- point clouds and laser scans in front of the inflated calls, 2-D and 3-D -----------------------------------------
+ * A depth sensor or a lidar delivers points, not voxels.  These are epic_hip_set_occupancy_inflated_* applied to a block B that is
+ * built from the points and never exists on the host: origin, extent, obstacle_threshold, no_change, flags, radius_sq, changed and
+ * kernel_ms mean what they mean there.
+ *   points   n_points x n floats in grid-cell units, (x, y[, z]) with x along the LAST axis of m: the order and the units of the
+ *            `points` of epic_hip_sample_potential_* -- one array serves both calls.  NULL with n_points == 0 changes nothing;
+ *   sensor   n floats in the same order, or NULL: no ray clearing.
+ *   1. a point's cell is the floor of each coordinate.  A point is finite when all n coordinates are; a coordinate of 2^31 or more
+ *      in magnitude has no cell and lies outside every box.  A HIT is a finite point whose cell lies inside the box [origin, origin
+ *      + extent);
+ *   2. with a sensor -- finite, its cell inside the box, so no ray is ever clipped -- every finite point casts a ray from the sensor's
+ *      cell to its own: sum_i |cell_i - sensor_cell_i| single-axis steps, each along the axis with the smallest f32 tMax among the
+ *      axes with steps to go (ties: the lowest axis in the order of m), stopping early where it leaves the box.  The start cell and
+ *      every cell entered before the end cell are CLEARED, the end cell is not.  tMax and tDelta are set up from the sensor and the
+ *      point themselves (the segment a beam travels), operation by operation in epic_amd/csrc/occupancy_points_rule.h;
+ *   3. B(c) = X (step 3 of the inflation rule) for the cell of a hit, 0 for a cleared cell that holds no hit, no_change everywhere
+ *      else; hits win whatever the order of the points.  So no_change must be a value of the byte type flags selects, and
+ *      0 < obstacle_threshold <= X;
+ *   4. the result is that of epic_hip_set_occupancy_inflated_* for B: u, the lock state, *changed, the cells never touched, the
+ *      ordering point, the EPIC_HIP_OCC_KEEP_FREE promise, radius_sq and its bound.
+ * EPIC_ERROR_INVALID_DATA with nothing touched: what the inflated call rejects; NULL points with n_points > 0; a sensor that is not
+ * finite or outside the box; a no_change or an obstacle_threshold outside the ranges of step 3; a box that reaches past 2^31 - 1.
+ * The _cpu variant builds B on the host and is the definition.  The _gpu variant uploads the points alone (n * 4 bytes each) and
+ * builds B on the device (occupancy_points.hip: two bit planes filled with in-wave merged atomics, expanded to bytes; the hit plane
+ * doubles as the inflation's source bits); *kernel_ms (may be NULL) is the device time of those kernels and the inflation's.
+ * Multi-device mode: B is built on the host and takes the inflated call's route, its n == 3 error included; *kernel_ms is 0. */
+int epic_hip_set_occupancy_points_cpu(EpicHarmonicT *h, unsigned int n_points, const float *points, const float *sensor /* may be NULL */,
+                                      const unsigned int *origin, const unsigned int *extent, int obstacle_threshold, int no_change,
+                                      unsigned flags, unsigned int radius_sq, unsigned long long *changed);
+int epic_hip_set_occupancy_points_gpu(EpicHarmonicT *h, unsigned int n_points, const float *points, const float *sensor /* may be NULL */,
+                                      const unsigned int *origin, const unsigned int *extent, int obstacle_threshold, int no_change,
+                                      unsigned flags, unsigned int radius_sq, unsigned long long *changed, float *kernel_ms /* may be NULL */);
+
 /* ---- Field queries: point samples, flow fields, cell read-back (2-D and 3-D) -----------------------------------------
  * Questions a caller asks of a relaxed field, answered where the field lives: harmonic->n is 2 or 3, and every call dispatches
  * on it.  The reference answers a request for one value by copying the whole field to the host

@@ -18,7 +18,10 @@ by harmonic_update_model_gpu, and for the 2-D window the whole-image call).  The
 --inflate map1024 map8192 win256 vox64 vox128 vox512: epic_hip_set_occupancy_inflated_gpu at radius_sq 9, 64 and 256 against the only
 route a caller had before it -- dilate the block on the host, then epic_hip_set_occupancy_region_gpu (run_inflate).
 
-    python tools/bench_occupancy.py [--sizes 1024 8192] [--regions vox512 box64 win256] [--inflate map1024 ...] [--calls 20] [--warmup 3]
+--points vox64 vox128 scan1024: epic_hip_set_occupancy_points_gpu (10^4 and 10^5 points in a 64^3 and a 128^3 box, a 720-beam scan on a
+1024^2 map; with and without a sensor, radius_sq 0 and 9) against a block built in numpy and epic_hip_set_occupancy_inflated_gpu (run_points).
+
+    python tools/bench_occupancy.py [--sizes 1024 8192] [--regions vox512 box64 win256] [--inflate map1024 ...] [--points vox64 ...] [--calls 20] [--warmup 3]
                                     [--out profiles/occupancy_ingest.txt]
 """
 import argparse
@@ -290,6 +293,73 @@ def run_inflate(name, radii=(9, 64, 256)):
     return "\n".join(out)
 
 
+POINTS = {"vox64": ([64, 64, 64], (10 ** 4, 10 ** 5)), "vox128": ([128, 128, 128], (10 ** 4, 10 ** 5)), "scan1024": ([1024, 1024], (720,))}
+
+
+def host_block(m, points, sensor):
+    """The block a caller builds in numpy today: 100 in the points' cells, 0 under samples every half cell along each beam, -2 elsewhere."""
+    e, block = np.array(m), np.full(m, -2, dtype=np.int8)
+
+    def mark(cells, value):
+        cells = cells.reshape(-1, len(m))[:, ::-1]
+        block[tuple(cells[np.all((cells >= 0) & (cells < e), axis=1)].T)] = value
+    if sensor is not None:
+        d = points - sensor
+        steps = int(np.ceil(2.0 * np.abs(d).max()))
+        for chunk in np.array_split(d, max(1, len(d) * steps // (1 << 22))):
+            mark(np.floor(sensor + (np.arange(steps, dtype=np.float32) / steps)[:, None, None] * chunk).astype(np.int64), 0)
+    mark(np.floor(points).astype(np.int64), 100)
+    return block
+
+
+def run_points(name, radii=(0, 9), rounds=3):
+    """epic_hip_set_occupancy_points_gpu against the route without it -- host_block, then epic_hip_set_occupancy_inflated_gpu --, the two
+    alternating in one process on the same previous state: the min of `rounds` wall times after one warm-up round, and their spread
+    (max - min); *kernel_ms of the points call (its kernels and the inflation's).  A cloud is a shell around the sensor in the middle."""
+    m, counts = POINTS[name]
+    n, rng = len(m), np.random.default_rng(7)
+    u0, l0 = synthetic_grid(m, 20240601, 0.05)
+    h = Harmonic()
+    h.set_grid(m, u0, l0)
+    for fn in (E.harmonic_initialize_dimension_size_gpu, E.harmonic_initialize_potential_values_gpu, E.harmonic_initialize_locked_gpu):
+        assert fn(h) == 0, fn.__name__
+    assert E.harmonic_initialize_gpu(h, NT) == 0
+    out, changed, ms, rule = [], ct.c_ulonglong(0), ct.c_float(0.0), (50, -2, 0)
+    for count in counts:
+        centre = np.full(n, 0.5 * m[-1] + 0.25, dtype=np.float32)
+        way = rng.normal(size=(count, n)) if n == 3 else np.stack([np.cos(np.arange(count) * 2 * np.pi / count), np.sin(np.arange(count) * 2 * np.pi / count)], axis=1)
+        way /= np.linalg.norm(way, axis=1, keepdims=True)
+        points = np.ascontiguousarray(centre + way * (m[-1] * rng.uniform(0.3, 0.47, size=(count, 1))), dtype=np.float32)
+        for sensor in (None, centre):
+            for r2 in radii:
+                t = {"host": [], "build": [], "device": []}
+                for i in range(rounds + 1):
+                    assert E.harmonic_update_model_gpu(h) == 0   # the previous state again (untimed)
+                    t0 = time.perf_counter()
+                    block = host_block(m, points, sensor)
+                    t1 = time.perf_counter()
+                    assert E.epic_hip_set_occupancy_inflated_gpu(h, block.ctypes.data, None, None, *rule, r2, ct.byref(changed), None) == 0
+                    t2 = time.perf_counter()
+                    assert E.harmonic_update_model_gpu(h) == 0
+                    t3 = time.perf_counter()
+                    assert E.epic_hip_set_occupancy_points_gpu(h, count, points.ctypes.data, None if sensor is None else sensor.ctypes.data, None, None, *rule, r2,
+                                                               ct.byref(changed), ct.byref(ms)) == 0
+                    t4 = time.perf_counter()
+                    if i > 0:
+                        for key, value in (("host", t2 - t0), ("build", t1 - t0), ("device", t4 - t3)):
+                            t[key].append(1e3 * value)
+                out.append("points %-8s %s, %6d points, sensor %-3s radius_sq %d (min of %d after 1)  changed %8d | host route %9.3f ms (spread %.3f; numpy block "
+                           "%9.3f ms) | points_gpu %7.3f ms (spread %.3f) | its kernels %7.4f ms | host / device %.1fx"
+                           % (name, "x".join(map(str, m)), count, "no" if sensor is None else "yes", r2, rounds, changed.value, min(t["host"]),
+                              max(t["host"]) - min(t["host"]), min(t["build"]), min(t["device"]), max(t["device"]) - min(t["device"]), ms.value,
+                              min(t["host"]) / min(t["device"])))
+                print("# " + out[-1], flush=True)
+    for fn in (E.harmonic_uninitialize_gpu, E.harmonic_uninitialize_dimension_size_gpu, E.harmonic_uninitialize_potential_values_gpu,
+               E.harmonic_uninitialize_locked_gpu):
+        assert fn(h) == 0, fn.__name__
+    return "\n".join(out)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", type=int, nargs="*", default=[1024, 8192])
@@ -298,6 +368,8 @@ def main():
                          "win256 a 256^2 window in 8192^2; each against the routes it replaces (run_region)")
     ap.add_argument("--inflate", nargs="*", choices=sorted(INFLATE), default=[],
                     help="epic_hip_set_occupancy_inflated_gpu at radius_sq 9, 64, 256 against dilating on the host (run_inflate)")
+    ap.add_argument("--points", nargs="*", choices=sorted(POINTS), default=[],
+                    help="epic_hip_set_occupancy_points_gpu against a numpy block and epic_hip_set_occupancy_inflated_gpu (run_points)")
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None, help="also append the lines to this file")
@@ -312,7 +384,7 @@ def main():
     print(head, flush=True)
     lines = [head]
     jobs = [lambda n=n: run(n, args.calls, args.warmup) for n in args.sizes] + [lambda r=r: run_region(r) for r in args.regions] + [
-        lambda r=r: run_inflate(r) for r in args.inflate]
+        lambda r=r: run_inflate(r) for r in args.inflate] + [lambda r=r: run_points(r) for r in args.points]
     for job in jobs:
         lines.append((args.label + " " if args.label else "") + job())
         print(lines[-1], flush=True)
