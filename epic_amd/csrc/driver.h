@@ -33,6 +33,8 @@
 //                        the same reason
 //   field_query_driver.hip  queries of a resident field (epic_hip_sample_*_gpu, epic_hip_flow_field_gpu, epic_hip_get_*_gpu): ordering
 //                        points that write nothing; kept out of the driver_* units for the same reason
+//   field_shift_driver.hip  the rolling-window shift of a resident field (epic_hip_shift_field_gpu): hands "current" over to the other
+//                        buffer and a second mask block; kept out of the driver_* units for the same reason
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>

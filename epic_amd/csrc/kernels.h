@@ -422,4 +422,13 @@ hipError_t launch_gather_region(const QueryField &field, const unsigned origin[3
                                 hipStream_t stream);
 hipError_t launch_gather_cells(const QueryField &field, unsigned k, const unsigned *d_v, float *d_u, unsigned *d_locked, hipStream_t stream);
 
+// ---- the rolling-window shift (field_shift.hip); called from field_shift_driver.hip only ------------------------------------
+// new(x) = old(x + shift) by the rule of field_shift_rule.h, values and lock bits in one launch: u_cur is read and u_other (the
+// other buffer of the pair, != u_cur) receives the whole shifted field, every cell up to the pitch -- border, face and padding cells
+// are copied through; maskw is read and maskw_out (a second block of mask_words_2d(m0 * m1, pitch) words, != maskw) receives the
+// lane masks.  plan: shift_plan()'s, not an all-zero shift.  The fused masks of a 2-D field are NOT rebuilt.
+struct ShiftPlan;
+hipError_t launch_field_shift(const float *u_cur, float *u_other, const uint32_t *maskw, uint32_t *maskw_out, const ShiftPlan &plan, int pitch,
+                              hipStream_t stream);
+
 }  // namespace epic_hip

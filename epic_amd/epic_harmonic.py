@@ -169,6 +169,9 @@ _SIGNATURES = {
                                           ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_float)),
     "epic_hip_reset_free_cells_3d_cpu": (_H,),
     "epic_hip_reset_free_cells_3d_gpu": (_H,),
+    # rolling windows: shift is n signed entries in the order of m, fill_type an EPIC_CELL_TYPE_*
+    "epic_hip_shift_field_cpu": (_H, ct.POINTER(ct.c_int), ct.c_uint, ct.POINTER(ct.c_ulonglong)),
+    "epic_hip_shift_field_gpu": (_H, ct.POINTER(ct.c_int), ct.c_uint, ct.POINTER(ct.c_ulonglong), ct.POINTER(ct.c_float)),
     # field queries: points are n floats each, cell lists n unsigned each, origin / extent n entries in the order of m
     "epic_hip_sample_potential_cpu": (_H, ct.c_uint, ct.c_void_p, ct.c_void_p, ct.c_void_p),
     "epic_hip_sample_potential_gpu": (_H, ct.c_uint, ct.c_void_p, ct.c_void_p, ct.c_void_p),

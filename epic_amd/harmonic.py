@@ -199,6 +199,30 @@ class Harmonic(eh.EpicHarmonic):
                     raise RuntimeError("epic_amd: %s failed with code %d" % (variant.__name__, rc))
         return int(changed.value)
 
+    def shift(self, shift, fill='free', process='gpu'):
+        """Move the field with a rolling window (epic_hip_shift_field_*, include/epic_hip.h): ``shift`` has n signed entries in
+        the order of m, how far the window moves; every interior cell takes the cell ``shift`` further on -- potential, lock
+        state, goals -- and the cells that come in are ``fill``: 'free' or 'obstacle'.  Ingest the new strips with
+        ``set_occupancy(..., origin=...)`` afterwards.  ``process`` as in ``set_occupancy``.  Returns ``kept``, the number of
+        interior cells that took an old cell."""
+        if process not in ('gpu', 'cpu', 'both'):
+            raise ValueError("process must be 'gpu', 'cpu' or 'both'")
+        if fill not in ('free', 'obstacle'):
+            raise ValueError("fill must be 'free' or 'obstacle'")
+        shift = np.ascontiguousarray(np.asarray(shift, dtype=np.int32)).reshape(-1)
+        if shift.size != int(self.n):
+            raise ValueError("shift has n = %d entries" % int(self.n))
+        fill_type = 2 if fill == 'free' else 1   # EPIC_CELL_TYPE_FREE / EPIC_CELL_TYPE_OBSTACLE
+        kept = ct.c_ulonglong(0)
+        args = (self, shift.ctypes.data_as(ct.POINTER(ct.c_int)), fill_type, ct.byref(kept))
+        for variant, tail, wanted in ((eh._epic.epic_hip_shift_field_cpu, (), ('cpu', 'both')),
+                                      (eh._epic.epic_hip_shift_field_gpu, (None,), ('gpu', 'both'))):
+            if process in wanted:
+                rc = variant(*args, *tail)
+                if rc != 0:
+                    raise RuntimeError("epic_amd: %s failed with code %d" % (variant.__name__, rc))
+        return int(kept.value)
+
     def reset_free_cells(self, process='gpu'):
         """Every unlocked interior cell back to EPIC_LOG_SPACE_FREE (the node's reset_free_cells service), on a 2-D or a 3-D
         grid; ``process`` as in ``set_occupancy``."""

@@ -331,6 +331,37 @@ int epic_hip_set_occupancy_points_gpu(EpicHarmonicT *h, unsigned int n_points, c
                                       const unsigned int *origin, const unsigned int *extent, int obstacle_threshold, int no_change,
                                       unsigned flags, unsigned int radius_sq, unsigned long long *changed, float *kernel_ms /* may be NULL */);
 
+/* ---- rolling windows: the field moves with the robot by whole cells, 2-D and 3-D ---------------------------------------
+ * A costmap with rolling_window, a voxel box centred on the robot: when the window has moved `shift` cells, the cells that stay
+ * inside keep their potential and their lock state at their new indices, and only the strips that came in need ingesting
+ * (epic_hip_set_occupancy_region_* on each).  Without this a caller reads the field back, rolls it and uploads it again.
+ *   shift      n signed entries in the order of m: how far the WINDOW moves along m[0], m[1][, m[2]];
+ *   fill_type  EPIC_CELL_TYPE_FREE (unlocked, u = EPIC_LOG_SPACE_FREE) or EPIC_CELL_TYPE_OBSTACLE (locked, u =
+ *              EPIC_LOG_SPACE_OBSTACLE) for the uncovered cells; any other value: EPIC_ERROR_INVALID_DATA with nothing touched.
+ *   1. new(x) = old(x + shift) for every INTERIOR cell x (not on the border in 2-D, not on any of the six faces in 3-D) whose source
+ *      x + shift, computed in 64 bits, is an interior cell of the grid: x takes its u -- the bit pattern, whatever it is -- and its
+ *      lock state.  A goal (locked, u == 0) moves like any other cell; one that scrolls out is gone;
+ *   2. every other interior cell is uncovered and takes the fill;
+ *   3. border and face cells are neither read as sources nor written: the device masks hold them locked whatever the host arrays
+ *      say, and reading interior sources only keeps the two in agreement;
+ *   4. *kept (may be NULL) receives the number of interior cells that took an old cell: prod_i max(0, m[i] - 2 - |shift[i]|),
+ *      without overflow for any int;
+ *   5. an all-zero shift succeeds, leaves the state bit for bit as it was and invalidates no work list; *kept is the interior count;
+ *   6. currentIteration, delta and epsilon are not touched.
+ * The _cpu variant edits harmonic->u and harmonic->locked and is the definition.  The _gpu variant edits the device-resident state
+ * only, in one launch (field_shift.hip: aligned 16-byte accesses realigned in registers, lock words funnel-shifted), and is an
+ * ordering point with the sequence of epic_hip_set_occupancy_region_gpu: pending iterations are flushed, the work goes onto the
+ * library's stream, the call synchronises, and the next two iterations run every tile unless the shift was all-zero.  Every later
+ * iteration, check, query, walk and read-back gives the bits a context freshly initialised from the _cpu result would give.
+ * *kernel_ms (may be NULL): the device time of the shift kernel alone, 0 where none ran.
+ * Multi-device mode (EPIC_HIP_DEVICES): slab versions are not built; the _gpu call returns EPIC_ERROR_INVALID_DATA with a message
+ * naming the host route, epic_hip_shift_field_cpu followed by harmonic_update_model_gpu, and changes nothing.
+ * EPIC_ERROR_INVALID_DATA: a null harmonic, m or shift; (_cpu) a null u or locked; n not 2 or 3; (_gpu) no device state; a bad
+ * fill_type.  HIP failures give the codes epic_hip_set_occupancy_region_gpu gives for the same steps. */
+int epic_hip_shift_field_cpu(EpicHarmonicT *h, const int *shift, unsigned int fill_type, unsigned long long *kept);
+int epic_hip_shift_field_gpu(EpicHarmonicT *h, const int *shift, unsigned int fill_type, unsigned long long *kept,
+                             float *kernel_ms /* may be NULL */);
+
 /* ---- Field queries: point samples, flow fields, cell read-back (2-D and 3-D) -----------------------------------------
  * Questions a caller asks of a relaxed field, answered where the field lives: harmonic->n is 2 or 3, and every call dispatches
  * on it.  The reference answers a request for one value by copying the whole field to the host
